@@ -15,6 +15,16 @@ After the last step the PixelData framebuffers are summed to rank 0 with one
 RCCL reduce over xGMI (inside the timed region).  Rays counted exactly as the
 reference's k_getNumRaysTraced (every traceRay incl. NEE shadow rays).
 
+A plain run does what the headline needs and no more: it maps the compiled
+scene that `--prepare-scene` kept (__graft_entry__.build() runs it; without it
+the run compiles the scene, ~36 s), uploads it, warms up, times the K steps,
+writes the image with `--dump-outputs DIR` and prints the result line.  A run
+of the default scene that had to compile it keeps it for the next run (2.7 GB
+in cudatracerlib_amd/_scene_cache/; --no-scene-cache neither reads nor writes).
+`--full` adds everything else after the timed steps: the instrumented pass and
+the roofline with its measured ceilings, the side legs, the committed parity
+records and the CPU baseline.
+
 Launch: python bench.py [--gpus N --steps K --warmup W].  For N>1 under
 torch.distributed.run (one process per GPU, RCCL backend); started as a plain
 `python bench.py --gpus N` the process starts that launcher as a child (before
@@ -105,6 +115,20 @@ def parse(argv=None):
     ap.add_argument("--launch-check", action="store_true",
                     help="launcher rehearsal: the ranks join the process group and count themselves; no GPU, "
                          "no scene (tests/test_bench_launch.py)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beside the headline: the instrumented pass and "
+                         "the roofline with its measured ceilings, the side legs (--*-passes, --*-leg, --anim-iters), "
+                         "the committed parity records and the CPU baseline.  A plain run sets up, warms up, times "
+                         "the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what they computed as DIR/<name>.npy: framebuffer.npy (the "
+                         "PixelData image the caller holds after the last step, float32 [width*height, 7]; rank 0's "
+                         "reduced image at N GPUs) and rays_traced.npy (float64 [1], all ranks)")
+    ap.add_argument("--no-scene-cache", action="store_true",
+                    help="one-process runs: compile the scene even when --prepare-scene left its compiled desc")
+    ap.add_argument("--prepare-scene", action="store_true",
+                    help="compile this run's scene, write it to the scene cache beside the library and exit "
+                         "(no GPU): later one-process runs with the same scene options map it instead of compiling")
     return ap.parse_args(argv)
 
 
@@ -718,6 +742,72 @@ def compile_scene(ctl, a, threads):
     return hs, hs.compile(threads=threads)
 
 
+def scene_threads():
+    """Host threads of the scene compile: the job's CPU share."""
+    return max(1, int(os.environ.get("OMP_NUM_THREADS", "8")))
+
+
+KEPT_SCENE_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "cudatracerlib_amd", "_scene_cache")
+
+
+def kept_scene_path(a, threads):
+    """The file that keeps a one-process run's compiled scene between runs
+    (`--prepare-scene`, which __graft_entry__.build() runs): one per set of
+    scene options, compile threads and source fingerprint of the library that
+    compiles it (buildid.py), so a scene compiled by other sources, with other
+    options or another thread count is never picked up."""
+    from buildid import source_fingerprint
+    key = f"c{a.config}_s{a.scale:g}_{a.width}x{a.height}_{a.builder}_{a.sbvh_alpha:g}_{a.split_alpha}_" \
+          f"{a.split_depth}_{a.bins}_{a.max_leaf}_t{threads}"
+    fp = source_fingerprint(os.path.dirname(os.path.abspath(__file__)))[:16]
+    return os.path.join(KEPT_SCENE_DIR, f"scene_{key}_{fp}.bin"), f"scene_{key}_"
+
+
+SCENE_OPTIONS = ("config", "scale", "width", "height", "builder", "sbvh_alpha", "split_alpha", "split_depth", "bins",
+                 "max_leaf")
+
+
+def is_default_scene(a):
+    """Whether the scene options are bench.py's defaults (the headline's scene)."""
+    d = parse([])
+    return all(getattr(a, k) == getattr(d, k) for k in SCENE_OPTIONS)
+
+
+def kept_scene(ctl, a, threads, write=False):
+    """The scene of a one-process run: the desc `--prepare-scene` kept (the same
+    bytes a compile gives, tests/test_bench_launch.py), mapped read-only, else a
+    compile (the SBVH build: ~36 s at C3 size), which `write` keeps for the
+    next run (--prepare-scene, and a run of the default scene that found none).
+    --no-scene-cache, or a library named by CTL_LIB (its sources are not this
+    tree's), always compiles.  Returns (owner, desc, source)."""
+    import glob
+    from cudatracerlib_amd import scene_cache
+    if a.no_scene_cache or os.environ.get("CTL_LIB"):
+        hs, desc = compile_scene(ctl, a, threads)
+        return hs, desc, "compiled"
+    path, stem = kept_scene_path(a, threads)
+    if os.path.exists(path):
+        try:
+            cached = scene_cache.load(path)
+            return cached, cached.desc, "mapped from the kept scene cache"
+        except (OSError, ValueError) as e:
+            log(f"bench: kept scene {path} not usable ({e}); compiling")
+    hs, desc = compile_scene(ctl, a, threads)
+    if not write:
+        return hs, desc, "compiled"
+    try:
+        os.makedirs(KEPT_SCENE_DIR, exist_ok=True)
+        for old in glob.glob(os.path.join(KEPT_SCENE_DIR, stem + "*")):   # the same scene of other sources
+            os.remove(old)
+        scene_cache.save(desc, path)
+        return hs, desc, "compiled (cache written)"
+    except OSError as e:          # no room: the next run compiles again
+        log(f"bench: scene cache not written ({e})")
+        for tmp in glob.glob(path + ".tmp*"):
+            os.remove(tmp)
+        return hs, desc, "compiled"
+
+
 def build_scene_once(ctl, a, rank, world, dist, threads):
     """The scene of this run.  One rank per node compiles it (the SBVH build:
     ~36 s on 16 threads and a 3.5 GB host scene at C3 size) and writes the
@@ -727,7 +817,10 @@ def build_scene_once(ctl, a, rank, world, dist, threads):
     with --no-build-once, every rank compiles.  Returns (owner, desc, source):
     owner keeps the desc's arrays alive (a HostScene or a mapped cache)."""
     from cudatracerlib_amd import scene_cache
-    if world == 1 or a.no_build_once:
+    if world == 1:
+        # the default scene is kept for the next run when no --prepare-scene left it
+        return kept_scene(ctl, a, threads, write=is_default_scene(a))
+    if a.no_build_once:
         hs, desc = compile_scene(ctl, a, threads)
         return hs, desc, "compiled"
     cpu = dist.new_group(backend="gloo")
@@ -763,12 +856,34 @@ def build_scene_once(ctl, a, rank, world, dist, threads):
     return hs, desc, "compiled"
 
 
+def dump_outputs(directory, image, total_rays):
+    """--dump-outputs: what the timed steps computed, as the caller of the pass
+    loop receives it, one .npy per array: the PixelData framebuffer after the
+    last timed step (float32 [width * height, 7]: the image the K steps
+    accumulated from zero; 58 MB at 1920x1080) and the rays they traced.  The
+    scene, the passes' indices and the sampler stream are fixed by the
+    arguments, so two builds run with the same arguments are comparable array
+    by array.  Returns the file names written."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {"framebuffer": np.ascontiguousarray(image, dtype=np.float32),
+              "rays_traced": np.array([total_rays], dtype=np.float64)}
+    if sum(v.nbytes for v in arrays.values()) > 64_000_000:
+        # a larger image: a fixed, seeded sample of its pixels (rows in ascending order)
+        keep = (64_000_000 - 1024) // (arrays["framebuffer"].shape[1] * 4)
+        rows = np.sort(np.random.default_rng(0x5EED).choice(arrays["framebuffer"].shape[0], keep, replace=False))
+        arrays["framebuffer"] = np.ascontiguousarray(arrays["framebuffer"][rows])
+    for name, v in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), v)
+    return sorted(name + ".npy" for name in arrays)
+
+
 def apply_bvh(ctl, desc, bvh):
     """The device tree format --bvh selects (a scene flag of the desc)."""
     desc.flags |= {"wide": 0, "binary": ctl.CTL_SCENE_BINARY_BVH, "wideq": ctl._abi.CTL_SCENE_WIDE_QUANT}[bvh]
 
 
-SCENE_SOURCES = ["compiled", "compiled (cache written)", "mapped from the node's scene cache"]
+SCENE_SOURCES = ["compiled", "compiled (cache written)", "mapped from the node's scene cache",
+                 "mapped from the kept scene cache"]
 
 
 def host_peak_rss_gb():
@@ -845,6 +960,7 @@ def launch_check(a, world, rank):
         import cudatracerlib_amd as ctl
         b = argparse.Namespace(**vars(a))
         b.config, b.scale, b.width, b.height = 2, 0.02, 64, 64
+        b.no_scene_cache = True   # a rehearsal keeps nothing
         tb = time.perf_counter()
         owner, desc, source = build_scene_once(ctl, b, rank, world, dist, 2)
         t_build = time.perf_counter() - tb
@@ -887,6 +1003,16 @@ def main(argv=None):
     if a.launch_check:
         launch_check(a, world, rank)
         return 0
+    if a.steps < 1 or a.warmup < 0:
+        log("bench: --steps must be at least 1 and --warmup at least 0")
+        return 2
+    if a.prepare_scene:
+        sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+        import cudatracerlib_amd as ctl
+        t0 = time.perf_counter()
+        _, desc, source = kept_scene(ctl, a, scene_threads(), write=True)
+        log(f"bench: scene config {a.config}: {desc.n_tri_data} tris, {source} in {time.perf_counter() - t0:.1f}s")
+        return 0
     # image-tile shards: one per rank, or N emulated ranks in this one process
     shards = a.emulate_ranks if (world == 1 and a.emulate_ranks > 1) else world
     tile_rank = rank   # the tile shard this process renders
@@ -918,7 +1044,7 @@ def main(argv=None):
             dist.init_process_group(a.backend)
     stream = torch.cuda.current_stream(dev)
     sptr = stream.cuda_stream
-    threads = max(1, int(os.environ.get("OMP_NUM_THREADS", "8")))
+    threads = scene_threads()
 
     t0 = time.perf_counter()
     hs, desc, scene_source = build_scene_once(ctl, a, rank, world, dist, threads)
@@ -937,11 +1063,13 @@ def main(argv=None):
     # Instrumented pass (same kernel compiled with counters, untimed) for the
     # roofline's algorithmic bytes: 64 B per inner node visited, 52 B per
     # triangle tested (48 B Woop + 4 B index), 108 B per instance entry
-    # (SURVEY.md §8d); per-launch = one pass over this rank's tiles.
-    scratch = torch.zeros_like(fb)
-    st = pt.pass_stats(scratch.data_ptr(), 1 << 40, sptr)
-    alg_bytes_per_pass = 64 * st[1] + 52 * st[2] + 108 * st[3]
-    del scratch
+    # (SURVEY.md §8d); per-launch = one pass over this rank's tiles.  A run of
+    # its own, so --full only.
+    if a.full:
+        scratch = torch.zeros_like(fb)
+        st = pt.pass_stats(scratch.data_ptr(), 1 << 40, sptr)
+        alg_bytes_per_pass = 64 * st[1] + 52 * st[2] + 108 * st[3]
+        del scratch
 
     pass_base = 0
     steps_done = 0
@@ -1019,34 +1147,38 @@ def main(argv=None):
     wsum = float(image[:, 6].sum().item()) if rank == 0 else 0.0   # the timed passes' image (before the legs)
 
     rays = pt.rays_traced()
-    prof = pmc_profile()
+    # --dump-outputs: the image as the timed steps left it (the legs below render into fb)
+    dump_image = image.cpu().numpy() if rank == 0 and a.dump_outputs else None
+    # everything below up to the rank report is beside the headline: --full only
+    full0 = a.full and rank == 0
+    prof = pmc_profile() if a.full else (None, None, False)
     nxt = pass_base + a.steps * shards
-    prim = primary_ray_leg(pt, dev, stream, sptr, torch, nxt, prof) if rank == 0 else None
+    prim = primary_ray_leg(pt, dev, stream, sptr, torch, nxt, prof) if full0 else None
     wpt = (wpt_leg(ctl, pt, dev, sptr, torch, W, H, nxt + 1, a.wpt_passes)
-           if rank == 0 and a.wpt_passes > 0 else None)
+           if full0 and a.wpt_passes > 0 else None)
     if wpt is not None:   # the same integrator with the any-hit shadow query (CTL_WPT_SHADOW_ANY_HIT)
         wpt["shadow_any_hit"] = wpt_leg(ctl, pt, dev, sptr, torch, W, H, nxt + 1, a.wpt_passes, flags=1)
     c1 = None
-    if rank == 0 and a.prim_passes > 0:
+    if full0 and a.prim_passes > 0:
         try:   # a side leg: its failure is reported in the line, not fatal to the headline
             c1 = c1_prim_leg(ctl, dev, torch, a.prim_passes)
         except Exception as e:
             c1 = {"error": f"{type(e).__name__}: {e}"}
     single = None
-    if rank == 0 and shards == 1 and G > 1 and a.one_pass_leg > 0:
+    if full0 and shards == 1 and G > 1 and a.one_pass_leg > 0:
         single = single_pass_leg(pt, fb, stream, sptr, torch, nxt + 40, a.one_pass_leg)
     dopass = None
-    if rank == 0 and shards == 1 and a.dopass_leg > 0:
+    if full0 and shards == 1 and a.dopass_leg > 0:
         dopass = reference_dopass_leg(pt, desc, fb, stream, sptr, torch, nxt + 60, a.dopass_leg)
         dopass["render_ahead"] = reference_dopass_leg(pt, desc, fb, stream, sptr, torch, nxt + 100,
                                                       max(16, a.dopass_leg), ahead=True)
     closest = None
-    if rank == 0 and a.closest_shadow_passes > 0 and shards == 1:
+    if full0 and a.closest_shadow_passes > 0 and shards == 1:
         scratch = torch.zeros_like(fb)
         closest = closest_shadow_leg(pt, scratch, stream, sptr, torch, nxt + 10, a.closest_shadow_passes)
         del scratch
     binary = None
-    if rank == 0 and shards == 1 and a.binary_passes > 0 and a.bvh == "wide":
+    if full0 and shards == 1 and a.binary_passes > 0 and a.bvh == "wide":
         try:   # a side leg: reported in the line, not fatal to the headline
             scratch = torch.zeros_like(fb)
             binary = binary_leg(ctl, pt, desc, scratch, stream, sptr, torch, nxt + 80, a.binary_passes)
@@ -1054,13 +1186,13 @@ def main(argv=None):
         except Exception as e:
             binary = {"error": f"{type(e).__name__}: {e}"}
     c5 = None
-    if rank == 0 and shards == 1 and a.c5_passes > 0 and a.config != 5:
+    if full0 and shards == 1 and a.c5_passes > 0 and a.config != 5:
         try:   # a side leg, like C1: reported in the line, not fatal to the headline
             c5 = c5_leg(ctl, dev, torch, stream, sptr, a, threads)
         except Exception as e:
             c5 = {"error": f"{type(e).__name__}: {e}"}
     anim = None
-    if rank == 0 and a.anim_iters > 0:
+    if full0 and a.anim_iters > 0:
         try:   # a side leg, like C1; last, so that it perturbs no other leg
             anim = animation_leg(ctl, dev, torch, a.anim_iters)
         except Exception as e:
@@ -1084,62 +1216,64 @@ def main(argv=None):
         launches = len(kev)   # path-kernel launches on this rank in the timed region
         per_launch_ms = kernel_ms / launches
         passes_per_launch = passes / launches   # this rank's passes (tiles of them when sharded) per launch
-        fam = "path_kernel_full" if a.config == 5 else "path_kernel"
-        # the profile's counters are per traced ray (rays_per_launch) and per pass, so
-        # they scale to this run's launch shape, a rank's share of a sharded image
-        # included (its launches trace 1/N of the image's rays of N passes); only the
-        # workload (scene, resolution, schedule, tree) must match
-        pj = prof[0] or {}
-        same_workload = ("passes_per_launch" in pj and list(pj.get("config", []))[:4] == [a.config, a.scale, W, H]
-                         and a.schedule == "persistent" and a.bvh == "wide")
-        pk = (pj.get("kernels") or {}).get(fam, {})
-        if pk.get("rays_per_launch"):
-            rl = roofline(prof if same_workload else (None, None, False), fam, per_launch_ms,
-                          alg_bytes_per_pass * passes_per_launch, KERNEL_NAME[a.schedule], units=rays / launches,
-                          unit_key="rays_per_launch")
-        else:
-            rl = roofline(prof if same_workload and pj.get("shards", 1) == shards else (None, None, False), fam,
-                          per_launch_ms, alg_bytes_per_pass * passes_per_launch, KERNEL_NAME[a.schedule],
-                          units=passes_per_launch)
-        rl.update({"launches_timed": launches, "gpu_step_ms": round(step_ms / a.steps, 3),
-                   "passes_per_launch": round(passes_per_launch, 4),
-                   "steps_per_launch": launch_groups(a.steps, G),
-                   "visits_per_launch": {"inner_nodes": int(st[1]), "tri_tests": int(st[2]),
-                                         "instances": int(st[3]), "rays": int(st[0])}})
-        if a.ceiling and rank == 0:
-            # the binding resources against their measured ceilings on this GPU
-            lanes = int(round(64 * rl["valu_lane_util"])) if rl.get("valu_lane_util") else 26
-            ce = measure_ceilings(local, lanes)
-            node_steps_s = st[1] * passes_per_launch / (per_launch_ms * 1e-3)
-            ce["path_kernel_node_steps_per_s"] = round(node_steps_s, 1)
-            nc = ce["node_chain"]
-            # against every probe: incoherent lanes (each its own random line: a floor the
-            # kernel's coherence lifts it above), coherent lanes over L2 (the chain at the L2
-            # hit latency, every step a miss in L1), coherent lanes over L1 (at the L1 latency)
-            ce["frac_chain_by_probe"] = {k: round(node_steps_s / v["lane_steps_per_s"], 4) for k, v in nc.items()}
-            ce["frac_chain"] = ce["frac_chain_by_probe"]["l2_resident_coherent"]
-            # triangle tests are dependent fetches too (three 16-B loads against the node's seven)
-            ce["frac_chain_with_tri_fetches"] = round(
-                (st[1] + st[2] * 3.0 / 7.0) * passes_per_launch / (per_launch_ms * 1e-3)
-                / nc["l2_resident_coherent"]["lane_steps_per_s"], 4)
-            if rl.get("achieved"):
-                ce["frac_hbm_of_measured_read"] = round(rl["achieved"] / ce["hbm_read_gbs"], 4)
-            ce["note"] = ("frac_chain = the path kernel's 4-wide node steps per second (STATS pass x passes per "
-                          "launch / its HIP-event launch time) over the dependent-chain probe at the kernel's lane "
-                          "activity and occupancy with the wave's lanes on one chain of L2-resident nodes (one line "
-                          "per load instruction; the kernel's L2 requests per vector-memory instruction are "
-                          "l2_requests_per_vmem_inst); the kernel also shades, tests triangles and idles in "
-                          "divergence, which the probe does not.  frac_chain_by_probe: against every probe")
-            pkk = ((prof[0] or {}).get("kernels") or {}).get(fam, {})
-            vm = (pkk.get("counters_per_launch") or {}).get("SQ_INSTS_VMEM_RD")
-            if pkk.get("l2_read_bytes") and vm:
-                ce["l2_requests_per_vmem_inst"] = round(pkk["l2_read_bytes"] / 128.0 / vm, 3)
-            rl["ceilings"] = ce
-            rl["hbm_ceiling_gbs"] = ce["hbm_read_gbs"]
-            rl["frac_chain"] = ce["frac_chain"]
-        if passes_per_launch > 1:
-            rl["launch"] = ("ctl_render_passes: the launch's sampler tables, one path-kernel launch over all its "
-                            "passes, slice fold (all inside the bracket)")
+        rl = None
+        if a.full:   # the roofline needs the instrumented pass and the committed counters
+            fam = "path_kernel_full" if a.config == 5 else "path_kernel"
+            # the profile's counters are per traced ray (rays_per_launch) and per pass, so
+            # they scale to this run's launch shape, a rank's share of a sharded image
+            # included (its launches trace 1/N of the image's rays of N passes); only the
+            # workload (scene, resolution, schedule, tree) must match
+            pj = prof[0] or {}
+            same_workload = ("passes_per_launch" in pj and list(pj.get("config", []))[:4] == [a.config, a.scale, W, H]
+                             and a.schedule == "persistent" and a.bvh == "wide")
+            pk = (pj.get("kernels") or {}).get(fam, {})
+            if pk.get("rays_per_launch"):
+                rl = roofline(prof if same_workload else (None, None, False), fam, per_launch_ms,
+                              alg_bytes_per_pass * passes_per_launch, KERNEL_NAME[a.schedule], units=rays / launches,
+                              unit_key="rays_per_launch")
+            else:
+                rl = roofline(prof if same_workload and pj.get("shards", 1) == shards else (None, None, False), fam,
+                              per_launch_ms, alg_bytes_per_pass * passes_per_launch, KERNEL_NAME[a.schedule],
+                              units=passes_per_launch)
+            rl.update({"launches_timed": launches, "gpu_step_ms": round(step_ms / a.steps, 3),
+                       "passes_per_launch": round(passes_per_launch, 4),
+                       "steps_per_launch": launch_groups(a.steps, G),
+                       "visits_per_launch": {"inner_nodes": int(st[1]), "tri_tests": int(st[2]),
+                                             "instances": int(st[3]), "rays": int(st[0])}})
+            if a.ceiling and rank == 0:
+                # the binding resources against their measured ceilings on this GPU
+                lanes = int(round(64 * rl["valu_lane_util"])) if rl.get("valu_lane_util") else 26
+                ce = measure_ceilings(local, lanes)
+                node_steps_s = st[1] * passes_per_launch / (per_launch_ms * 1e-3)
+                ce["path_kernel_node_steps_per_s"] = round(node_steps_s, 1)
+                nc = ce["node_chain"]
+                # against every probe: incoherent lanes (each its own random line: a floor the
+                # kernel's coherence lifts it above), coherent lanes over L2 (the chain at the L2
+                # hit latency, every step a miss in L1), coherent lanes over L1 (at the L1 latency)
+                ce["frac_chain_by_probe"] = {k: round(node_steps_s / v["lane_steps_per_s"], 4) for k, v in nc.items()}
+                ce["frac_chain"] = ce["frac_chain_by_probe"]["l2_resident_coherent"]
+                # triangle tests are dependent fetches too (three 16-B loads against the node's seven)
+                ce["frac_chain_with_tri_fetches"] = round(
+                    (st[1] + st[2] * 3.0 / 7.0) * passes_per_launch / (per_launch_ms * 1e-3)
+                    / nc["l2_resident_coherent"]["lane_steps_per_s"], 4)
+                if rl.get("achieved"):
+                    ce["frac_hbm_of_measured_read"] = round(rl["achieved"] / ce["hbm_read_gbs"], 4)
+                ce["note"] = ("frac_chain = the path kernel's 4-wide node steps per second (STATS pass x passes per "
+                              "launch / its HIP-event launch time) over the dependent-chain probe at the kernel's "
+                              "lane activity and occupancy with the wave's lanes on one chain of L2-resident nodes "
+                              "(one line per load instruction; the kernel's L2 requests per vector-memory instruction are "
+                              "l2_requests_per_vmem_inst); the kernel also shades, tests triangles and idles in "
+                              "divergence, which the probe does not.  frac_chain_by_probe: against every probe")
+                pkk = ((prof[0] or {}).get("kernels") or {}).get(fam, {})
+                vm = (pkk.get("counters_per_launch") or {}).get("SQ_INSTS_VMEM_RD")
+                if pkk.get("l2_read_bytes") and vm:
+                    ce["l2_requests_per_vmem_inst"] = round(pkk["l2_read_bytes"] / 128.0 / vm, 3)
+                rl["ceilings"] = ce
+                rl["hbm_ceiling_gbs"] = ce["hbm_read_gbs"]
+                rl["frac_chain"] = ce["frac_chain"]
+            if passes_per_launch > 1:
+                rl["launch"] = ("ctl_render_passes: the launch's sampler tables, one path-kernel launch over all its "
+                                "passes, slice fold (all inside the bracket)")
         out = {
             "metric": "Mrays/s (primary+secondary) at 1920x1080, San-Miguel-scale BVH",
             "value": round(total_rays / elapsed / 1e6, 3),
@@ -1170,22 +1304,29 @@ def main(argv=None):
                 "total_rays": total_rays,
                 **({"emulated_ranks": shards, "emulated_rank": tile_rank} if shards != world else {}),
             },
-            "roofline": rl,
             "ranks": ranks,
-            "primary_rays": prim,
-            "one_pass_launches": single,
-            "reference_dopass": dopass,
-            "closest_hit_shadows": closest,
-            "binary_bvh": binary,
-            "parity_vs_reference_order": reference_order_record(),
-            "wavefront_tracer": wpt,
-            "prim_tracer_c1": c1,
-            "animation": anim,
-            "path_tracer_c5": c5,
             "image_weight_sum": wsum,
             "scene_build_s": round(t_build, 2),
+            "scene_source": scene_source,
+            "full": bool(a.full),
         }
-        if world == 1 and not a.no_cpu_baseline:
+        if a.dump_outputs:
+            out["dumped"] = dump_outputs(a.dump_outputs, dump_image, total_rays)
+        if a.full:
+            out.update({
+                "roofline": rl,
+                "primary_rays": prim,
+                "one_pass_launches": single,
+                "reference_dopass": dopass,
+                "closest_hit_shadows": closest,
+                "binary_bvh": binary,
+                "parity_vs_reference_order": reference_order_record(),
+                "wavefront_tracer": wpt,
+                "prim_tracer_c1": c1,
+                "animation": anim,
+                "path_tracer_c5": c5,
+            })
+        if a.full and world == 1 and not a.no_cpu_baseline:
             cc = cpu_cores()
             # the reference's CPU path runs on its own tree: SBVH with leaves <= 8
             # (SplitBVHBuilder Platform, BVHBuilderHelper.cpp:119), the same triangles

@@ -8,6 +8,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -110,6 +111,68 @@ def test_launch_groups_near_equal():
     for steps in range(1, 70):
         g = bench.launch_groups(steps, 8)
         assert sum(g) == steps and max(g) - min(g) <= 1 and max(g) <= 8
+
+
+def test_plain_run_is_the_default_and_full_is_an_option():
+    a = bench.parse(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 3 and a.warmup == 1
+    assert bench.parse(["--full"]).full is True
+    assert sum(bench.launch_groups(a.steps, a.steps_per_launch)) == 3   # --steps is the number of timed steps
+
+
+def test_dump_outputs_writes_float32_arrays_within_64_mb(tmp_path):
+    img = np.arange(5 * 7, dtype=np.float32).reshape(5, 7)
+    names = bench.dump_outputs(str(tmp_path / "d"), img, 123456789012)
+    assert names == ["framebuffer.npy", "rays_traced.npy"]
+    fb = np.load(tmp_path / "d" / "framebuffer.npy")
+    assert fb.dtype == np.float32 and np.array_equal(fb, img)
+    rays = np.load(tmp_path / "d" / "rays_traced.npy")
+    assert rays.dtype == np.float64 and rays.tolist() == [123456789012.0]
+    # an image over the limit: the same seeded sample of its rows every time, under 64 MB in all
+    big = np.zeros((2_400_000, 7), np.float32)
+    big[:, 0] = np.arange(big.shape[0], dtype=np.float32)
+    bench.dump_outputs(str(tmp_path / "a"), big, 1)
+    bench.dump_outputs(str(tmp_path / "b"), big, 1)
+    sa, sb = np.load(tmp_path / "a" / "framebuffer.npy"), np.load(tmp_path / "b" / "framebuffer.npy")
+    assert np.array_equal(sa, sb) and sa.dtype == np.float32 and np.all(np.diff(sa[:, 0]) > 0)
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 64_000_000
+
+
+def test_kept_scene_is_the_compiled_scene(tmp_path, monkeypatch):
+    """--prepare-scene keeps the compiled desc; a later run maps the same bytes.
+    The file is keyed by the scene options, the threads and the library's source
+    fingerprint, and CTL_LIB or --no-scene-cache compile."""
+    import ctypes as C
+    import cudatracerlib_amd as ctl
+    from cudatracerlib_amd import scene_cache
+    monkeypatch.setattr(bench, "KEPT_SCENE_DIR", str(tmp_path))
+    monkeypatch.delenv("CTL_LIB", raising=False)
+    a = bench.parse(["--config", "2", "--scale", "0.02", "--width", "64", "--height", "64"])
+
+    def digest(desc):
+        out = [bytes(desc.camera)]
+        for name, (et, count) in scene_cache._ARRAYS.items():
+            p = scene_cache._addr(getattr(desc, name))
+            out.append(C.string_at(p, C.sizeof(et) * int(count(desc))) if p else b"")
+        return out
+
+    # only a run of the default scene keeps what it had to compile
+    assert bench.is_default_scene(bench.parse(["--steps", "3", "--full"])) and not bench.is_default_scene(a)
+    hs0, d0, src0 = bench.kept_scene(ctl, a, 2)
+    assert src0 == "compiled" and not list(tmp_path.iterdir())
+    stale = tmp_path / (bench.kept_scene_path(a, 2)[1] + "0123456789abcdef.bin")
+    stale.write_bytes(b"other sources")
+    hs1, d1, src1 = bench.kept_scene(ctl, a, 2, write=True)
+    path = bench.kept_scene_path(a, 2)[0]
+    assert src1 == "compiled (cache written)" and [str(p) for p in tmp_path.iterdir()] == [path]
+    own2, d2, src2 = bench.kept_scene(ctl, a, 2)
+    assert src2 == "mapped from the kept scene cache" and digest(d2) == digest(d1) == digest(d0)
+    assert bench.kept_scene_path(a, 3)[0] != path                    # other threads: another file
+    b = bench.parse(["--config", "2", "--scale", "0.02", "--width", "64", "--height", "64", "--no-scene-cache"])
+    assert bench.kept_scene(ctl, b, 2)[2] == "compiled"
+    monkeypatch.setenv("CTL_LIB", "elsewhere.so")
+    assert bench.kept_scene(ctl, a, 2)[2] == "compiled"
+    own2.close()
 
 
 @pytest.mark.parametrize("rank", [-1, 8])
