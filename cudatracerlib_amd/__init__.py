@@ -200,6 +200,57 @@ class HostScene:
                 f.write(data)
         return data
 
+    def write_animated_xmsh(self, mesh, path=None):
+        """Animated mesh `mesh` of the last compile as an Animated .xmsh stream (type 1:
+        the compiled body, then its animations, AnimatedVertex records and triangles)."""
+        n = C.c_uint64(0)
+        _check(self._L.ctl_host_scene_write_animated_xmsh(self._h, int(mesh), None, 0, C.byref(n)), None,
+               "write_animated_xmsh")
+        buf = C.create_string_buffer(n.value)
+        _check(self._L.ctl_host_scene_write_animated_xmsh(self._h, int(mesh), buf, n.value, C.byref(n)), None,
+               "write_animated_xmsh")
+        data = buf.raw[:n.value]
+        if path is not None:
+            with open(path, "wb") as f:
+                f.write(data)
+        return data
+
+    def set_animated_bvh(self, mode):
+        """0 (default): skinned meshes compile with the binned builder, no splits;
+        1: with the scene's builder (set_bvh_builder / set_bvh_params)."""
+        _check(self._L.ctl_host_scene_set_animated_bvh(self._h, int(mode)), None, "set_animated_bvh")
+        return self
+
+    def add_animation(self, mesh, name, frame_rate, frames):
+        """Animation of an animated mesh: frames = (n_frames, n_bones, 4, 4) bone matrices.
+        Returns its index in the mesh."""
+        f = np.ascontiguousarray(frames, dtype=np.float32)
+        if f.ndim != 4 or f.shape[2:] != (4, 4):
+            raise ValueError("frames must be (n_frames, n_bones, 4, 4)")
+        r = self._L.ctl_host_scene_add_animation(self._h, int(mesh), name.encode(), int(frame_rate), f.ctypes.data,
+                                                 f.shape[0], f.shape[1])
+        if r < 0:
+            _check(1, None, "add_animation")
+        return r
+
+    def animations(self, mesh):
+        """The animations of mesh `mesh` (added or read from an Animated .xmsh): a list of
+        dicts {name, frame_rate, frames: (n_frames, n_bones, 4, 4) float32}."""
+        n = self._L.ctl_host_scene_animation_count(self._h, int(mesh))
+        if n < 0:
+            _check(1, None, "animations")
+        out = []
+        for a in range(n):
+            name = C.create_string_buffer(128)
+            rate, nf, nb = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+            _check(self._L.ctl_host_scene_animation_info(self._h, int(mesh), a, name, C.byref(rate), C.byref(nf),
+                                                         C.byref(nb)), None, "animations")
+            m = np.zeros((nf.value, nb.value, 4, 4), np.float32)
+            _check(self._L.ctl_host_scene_animation_frames(self._h, int(mesh), a, m.ctypes.data,
+                                                           nf.value * nb.value), None, "animations")
+            out.append({"name": name.value.decode(), "frame_rate": rate.value, "frames": m})
+        return out
+
     def add_node(self, mesh, xf16=None):
         arr = None
         if xf16 is not None:
@@ -261,6 +312,14 @@ class HostScene:
         _check(self._L.ctl_host_scene_compile(self._h, threads, C.byref(d)), None, "ctl_host_scene_compile")
         self.desc = d
         return d
+
+
+def animation_frame_index(frame_rate, n_frames, t):
+    """(frame, lerp) of AnimatedMesh::ComputeFrameIndex (ctl_animation_frame_index)."""
+    frame, lerp = C.c_uint32(0), C.c_float(0.0)
+    _check(lib().ctl_animation_frame_index(int(frame_rate), int(n_frames), float(t), C.byref(frame), C.byref(lerp)),
+           None, "ctl_animation_frame_index")
+    return frame.value, lerp.value
 
 
 def bvh_stack_bound(nodes, root_value=0):
@@ -356,6 +415,41 @@ class Tracer:
             raise ValueError("frames differ in bone count")
         _check(self._L.ctl_scene_animate(self._ctx, int(anim), f0.ctypes.data, f1.ctypes.data, f0.shape[0],
                                          float(lerp), stream), self._ctx, "ctl_scene_animate")
+
+    def set_animation(self, anim, animation, frames, frame_rate=0):
+        """Keeps animation `animation` of animated mesh `anim` on the device
+        (ctl_scene_set_animation): frames = (n_frames, n_bones, 4, 4).  Call after upload_scene."""
+        f = np.ascontiguousarray(frames, dtype=np.float32)
+        if f.ndim != 4 or f.shape[2:] != (4, 4):
+            raise ValueError("frames must be (n_frames, n_bones, 4, 4)")
+        _check(self._L.ctl_scene_set_animation(self._ctx, int(anim), int(animation), f.ctypes.data, f.shape[0],
+                                               f.shape[1]), self._ctx, "ctl_scene_set_animation")
+        self._anim_rates = getattr(self, "_anim_rates", {})
+        self._anim_rates[(int(anim), int(animation))] = int(frame_rate)
+
+    def upload_animations(self, host_scene):
+        """Every animation of every animated mesh of host_scene's last compile, made
+        resident (set_animation); the scene must have been uploaded from that compile."""
+        d = host_scene.desc
+        if d is None:
+            raise CTLError("upload_animations: compile the host scene first")
+        for a in range(d.n_anim_meshes):
+            for k, an in enumerate(host_scene.animations(d.anim_meshes[a].mesh)):
+                self.set_animation(a, k, an["frames"], an["frame_rate"])
+
+    def animate_frame(self, anim, animation, frame, lerp, stream=0):
+        """AnimatedMesh::k_ComputeState(animation, frame, lerp) from the resident frames:
+        skins between `frame` and (frame + 1) % n_frames."""
+        _check(self._L.ctl_scene_animate_frame(self._ctx, int(anim), int(animation), int(frame), float(lerp), stream),
+               self._ctx, "ctl_scene_animate_frame")
+
+    def animate_time(self, anim, animation, t, frame_rate=None, stream=0):
+        """animate_frame at time t (seconds): frame and lerp from ctl_animation_frame_index at
+        the animation's frame rate (the one set_animation / upload_animations recorded)."""
+        if frame_rate is None:
+            frame_rate = getattr(self, "_anim_rates", {}).get((int(anim), int(animation)), 0)
+        _check(self._L.ctl_scene_animate_time(self._ctx, int(anim), int(animation), int(frame_rate), float(t), stream),
+               self._ctx, "ctl_scene_animate_time")
 
     def read_array(self, which, first, count, dtype, width):
         """Device scene array slice (ctl_scene_read) as a (count, width) numpy array."""

@@ -262,6 +262,19 @@ SYMBOLS = [
     ("ctl_scene_read", C.c_int32, [_vp, C.c_uint32, C.c_uint64, C.c_uint64, _vp]),
     ("ctl_host_scene_add_xmsh", C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32]),
     ("ctl_host_scene_write_xmsh", C.c_int32, [_vp, C.c_uint32, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    ("ctl_host_scene_write_animated_xmsh", C.c_int32, [_vp, C.c_uint32, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    ("ctl_host_scene_set_animated_bvh", C.c_int32, [_vp, C.c_uint32]),
+    ("ctl_host_scene_add_animation", C.c_int32, [_vp, C.c_uint32, C.c_char_p, C.c_uint32, _vp, C.c_uint32,
+                                                 C.c_uint32]),
+    ("ctl_host_scene_animation_count", C.c_int32, [_vp, C.c_uint32]),
+    ("ctl_host_scene_animation_info", C.c_int32, [_vp, C.c_uint32, C.c_uint32, _vp, C.POINTER(C.c_uint32),
+                                                  C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    ("ctl_host_scene_animation_frames", C.c_int32, [_vp, C.c_uint32, C.c_uint32, _vp, C.c_uint64]),
+    ("ctl_animation_frame_index", C.c_int32, [C.c_uint32, C.c_uint32, C.c_float, C.POINTER(C.c_uint32),
+                                              C.POINTER(C.c_float)]),
+    ("ctl_scene_set_animation", C.c_int32, [_vp, C.c_uint32, C.c_uint32, _vp, C.c_uint32, C.c_uint32]),
+    ("ctl_scene_animate_frame", C.c_int32, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, _vp]),
+    ("ctl_scene_animate_time", C.c_int32, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, _vp]),
     ("ctl_host_last_error", C.c_char_p, []),
     ("ctl_host_scene_generate", C.c_int32, [_vp, C.c_int32, C.c_double, C.c_uint32, C.c_uint32]),
 ]

@@ -6,10 +6,11 @@
 //            matrix blends, TransformPoint / TransformDirection, lerp
 //   tris     g_ComputeTriangles -> TriangleData::setData (TriangleData.cu:35-63)
 //   rebuild  the mesh tree as BVHRebuilder::Build(&p, true) leaves it
-//            (AnimatedMesh.cpp:174-176, BVHRebuilder.cpp:281-340, 365-450): one
-//            thread per leaf (or per pair of leaves under one node) writes its
+//            (AnimatedMesh.cpp:174-176, BVHRebuilder.cpp:281-340, 365-450): the
 //            entries' Woop data (AnimProvider::setObject, AnimatedMesh.cpp:
-//            113-117) and the leaf's box record, then climbs: the last of a
+//            113-117) and each leaf's box record (one thread per leaf, or per
+//            entry on trees of long leaves: MeshRebuild::entry_woop), then one
+//            thread per leaf (or per pair of leaves under one node) climbs: the last of a
 //            node's children to arrive (an atomic counter per node) recomputes
 //            the node -- the best of the four child/grandchild rotations by SAH
 //            if strictly cheaper (host/bvh_rebuild.h states the rules), the
@@ -30,6 +31,12 @@
 //            along the moved instances' paths (SceneBVH::Build, the same
 //            BVHRebuilder without invalidateAll), its 4-wide copy refit in its
 //            topology, both uploaded.
+// The bone matrices come from host memory (ctl_scene_animate) or from an
+// animation's frames kept on the device (ctl_scene_set_animation, then
+// ctl_scene_animate_frame / _time: k_ComputeState's own signature); everything
+// after the two bone pointers is one function (animate_device).  The trees may
+// be the reference's own (an Animated .xmsh): leaves of any length, a triangle
+// in several leaves, empty child words anywhere.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -50,7 +57,13 @@ namespace ctl {
 struct MeshRebuild {
     uint32_t n_nodes = 0;               // binary nodes of the mesh tree
     uint32_t n_leaf = 0;
-    uint4* d_leaf = nullptr;            // {holder << 1 | slot, first entry, entries, pairing} (anim_rebuild_kernel)
+    // The Woop / leaf-record phase by the tree's shape, fixed by the plan: one
+    // thread per entry (anim_entry_kernel) from a mean of 3 entries per leaf,
+    // one thread per leaf (anim_leaf_kernel) below.  Measured per animate on
+    // the 2 M-triangle grid (profiles/r07_anim_xmsh.json): 4-entry leaves 0.424
+    // against 0.455 ms, 2-entry leaves (the binned default) 0.559 against 0.545.
+    bool entry_woop = false;
+    uint4* d_leaf = nullptr;           // {holder << 1 | slot, first entry, entries, pairing} (anim_rebuild_kernel)
     uint32_t* d_leaf_of = nullptr;      // per entry of the mesh: the record of the leaf starting there
     float* d_nrec = nullptr;            // per binary node: its box (6) and numLeafs (bvhNodeData), 32 B
     float* d_lrec = nullptr;            // per leaf: its box and entries, 32 B
@@ -64,8 +77,17 @@ struct MeshRebuild {
     uint4* d_wcode = nullptr;           // per 4-wide node: its child codes (WideArgs)
 };
 
+// An animation's frames on the device (ctl_scene_set_animation): n_frames x
+// n_bones float4x4, frame after frame.
+struct ResidentAnimation {
+    float* d = nullptr;
+    uint32_t n_frames = 0, n_bones = 0;
+};
+constexpr uint32_t kMaxAnimations = 1u << 16;
+
 struct AnimMeshPlan {
     ctl_anim_mesh am;
+    std::vector<ResidentAnimation> resident;   // by animation index; freed with the state (allocs)
     ctl_kernel_mesh km;
     uint32_t n_entries = 0;
     uint32_t wide_base = 0;             // the mesh's first wide node
@@ -251,7 +273,7 @@ struct RebuildArgs {
     float* lrec;                // per leaf record, the same: written by anim_leaf_kernel
     uint32_t* cnt;
     float* mesh_box;            // m_sLocalBox: 6 floats
-    uint32_t n_leaf, n_nodes;
+    uint32_t n_leaf, n_nodes, n_entries;
 };
 
 __device__ __forceinline__ Coh coh_of(const RebuildArgs& A) {
@@ -459,6 +481,40 @@ __global__ __launch_bounds__(kAB) void anim_leaf_kernel(RebuildArgs A) {
     float4* r = reinterpret_cast<float4*>(A.lrec + 8 * (size_t)i);
     r[0] = make_float4(lo[0], lo[1], lo[2], hi[0]);
     r[1] = make_float4(hi[1], hi[2], __int_as_float((int)lf.z), 0.0f);
+}
+
+// The same, one thread per entry: each writes its entry's Woop record (the
+// wave's stores are contiguous, 48 B per lane), and the thread of a leaf's
+// first entry forms the leaf's record over the leaf's entries in entry order
+// (AABB::Extend is order-dependent where -0.0 meets +0.0), re-reading the
+// vertices its neighbours just read.
+__global__ __launch_bounds__(kAB) void anim_entry_kernel(RebuildArgs A) {
+    const uint32_t e = blockIdx.x * kAB + threadIdx.x;
+    if (e >= A.n_entries) return;
+    {
+        const uint32_t t = A.idx[e] >> 1;
+        const f3 a = ld3(A.P, A.tris[3 * t]), b = ld3(A.P, A.tris[3 * t + 1]), c = ld3(A.P, A.tris[3 * t + 2]);
+        float w[12];
+        woop_set_hd(a, b, c, w);
+        A.woop[3 * e] = make_float4(w[0], w[1], w[2], w[3]);
+        A.woop[3 * e + 1] = make_float4(w[4], w[5], w[6], w[7]);
+        A.woop[3 * e + 2] = make_float4(w[8], w[9], w[10], w[11]);
+    }
+    const uint32_t i = A.leaf_of[e];
+    if (i == 0xffffffffu) return;
+    const uint32_t n = A.leaf[i].z;
+    float lo[3], hi[3];
+    box_empty(lo, hi);
+    for (uint32_t q = e; q < e + n; q++) {
+        const uint32_t t = A.idx[q] >> 1;
+        const f3 a = ld3(A.P, A.tris[3 * t]), b = ld3(A.P, A.tris[3 * t + 1]), c = ld3(A.P, A.tris[3 * t + 2]);
+        const float q0[3] = {tmin(tmin(a.x, b.x), c.x), tmin(tmin(a.y, b.y), c.y), tmin(tmin(a.z, b.z), c.z)};
+        const float q1[3] = {tmax(tmax(a.x, b.x), c.x), tmax(tmax(a.y, b.y), c.y), tmax(tmax(a.z, b.z), c.z)};
+        box_extend(lo, hi, q0, q1);
+    }
+    float4* r = reinterpret_cast<float4*>(A.lrec + 8 * (size_t)i);
+    r[0] = make_float4(lo[0], lo[1], lo[2], hi[0]);
+    r[1] = make_float4(hi[1], hi[2], __int_as_float((int)n), 0.0f);
 }
 
 // One thread per leaf (or leaf pair) whose record the leaf launch wrote, up the
@@ -822,6 +878,7 @@ bool plan_mesh(AnimState* A, MeshRebuild& R, const ctl_bvh_node* nodes, uint32_t
         }
     }
     R.n_leaf = (uint32_t)leaves.size();
+    R.entry_woop = n_entries >= 3ull * leaves.size();
     R.n_wide = n_wide;
     if (!anim_upload(A, &R.d_leaf, leaves.data(), leaves.size()) ||
         !anim_upload(A, &R.d_leaf_of, leaf_of.data(), leaf_of.size()) || !anim_alloc(A, &R.d_nrec, 8ull * n_nodes) ||
@@ -1013,16 +1070,31 @@ using namespace ctl;
 
 extern "C" {
 
+// the mesh, bone count and device checks every animate entry point shares
+static ctl_status animate_check(ctl_ctx* c, uint32_t anim, uint32_t n_bones, const char* what) {
+    if (!c->has_scene || !c->anim) { c->err = std::string(what) + ": no scene uploaded"; return CTL_ERR_STATE; }
+    AnimState* A = c->anim;
+    if (anim >= A->meshes.size()) { c->err = std::string(what) + ": animated mesh index out of range"; return CTL_ERR_INVALID; }
+    if (A->meshes[anim].am.max_bone >= n_bones) {
+        c->err = std::string(what) + ": a vertex uses a bone index >= n_bones";
+        return CTL_ERR_INVALID;
+    }
+    if (n_bones > 256) { c->err = std::string(what) + ": more than 256 bones (bone indices are 8-bit)"; return CTL_ERR_INVALID; }
+    if (hipSetDevice(c->device) != hipSuccess) { c->err = std::string(what) + ": hipSetDevice failed"; return CTL_ERR_HIP; }
+    return CTL_OK;
+}
+
+// k_ComputeState between the bone matrices b0 and b1 (device memory, n_bones
+// float4x4 each): everything after the bone pointers, for every entry point
+static ctl_status animate_device(ctl_ctx* c, uint32_t anim, const float* b0, const float* b1, uint32_t n_bones,
+                                 float lerp, hipStream_t s, const char* what);
+
 CTL_API ctl_status ctl_scene_animate(ctl_ctx* c, uint32_t anim, const ctl_float4x4* frame0, const ctl_float4x4* frame1,
                                      uint32_t n_bones, float lerp, void* stream) {
     if (!c || !frame0 || !frame1 || n_bones == 0) return CTL_ERR_INVALID;
-    if (!c->has_scene || !c->anim) { c->err = "scene_animate: no scene uploaded"; return CTL_ERR_STATE; }
+    const ctl_status ok = animate_check(c, anim, n_bones, "scene_animate");
+    if (ok != CTL_OK) return ok;
     AnimState* A = c->anim;
-    if (anim >= A->meshes.size()) { c->err = "scene_animate: animated mesh index out of range"; return CTL_ERR_INVALID; }
-    const AnimMeshPlan& P = A->meshes[anim];
-    if (P.am.max_bone >= n_bones) { c->err = "scene_animate: a vertex uses a bone index >= n_bones"; return CTL_ERR_INVALID; }
-    if (n_bones > 256) { c->err = "scene_animate: more than 256 bones (bone indices are 8-bit)"; return CTL_ERR_INVALID; }
-    if (hipSetDevice(c->device) != hipSuccess) { c->err = "scene_animate: hipSetDevice failed"; return CTL_ERR_HIP; }
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const size_t nb = 16ull * n_bones;
     if (A->bones_cap < nb) {
@@ -1038,12 +1110,85 @@ CTL_API ctl_status ctl_scene_animate(ctl_ctx* c, uint32_t anim, const ctl_float4
         c->err = "scene_animate: bone upload failed";
         return CTL_ERR_HIP;
     }
+    return animate_device(c, anim, A->d_bones[0], A->d_bones[1], n_bones, lerp, s, "scene_animate");
+}
+
+CTL_API ctl_status ctl_scene_set_animation(ctl_ctx* c, uint32_t anim, uint32_t animation, const ctl_float4x4* frames,
+                                           uint32_t n_frames, uint32_t n_bones) {
+    if (!c || !frames) return CTL_ERR_INVALID;
+    if (n_frames == 0 || n_bones == 0 || animation >= kMaxAnimations) {
+        c->err = "scene_set_animation: needs at least one frame and one bone (animation index < 65536)";
+        return CTL_ERR_INVALID;
+    }
+    const ctl_status ok = animate_check(c, anim, n_bones, "scene_set_animation");
+    if (ok != CTL_OK) return ok;
+    AnimState* A = c->anim;
+    AnimMeshPlan& P = A->meshes[anim];
+    if (P.resident.size() <= animation) P.resident.resize(animation + 1);
+    ResidentAnimation& R = P.resident[animation];
+    const size_t n = 16ull * n_frames * n_bones;
+    float* d = nullptr;
+    if (hipDeviceSynchronize() != hipSuccess) { c->err = "scene_set_animation: sync failed"; return CTL_ERR_HIP; }
+    if (!anim_alloc(A, &d, n)) { c->err = "scene_set_animation: frame table allocation failed"; return CTL_ERR_NOMEM; }
+    if (hipMemcpy(d, frames, n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+        c->err = "scene_set_animation: frame table upload failed";
+        return CTL_ERR_HIP;
+    }
+    if (R.d) {   // replaced: nothing in flight reads it after the synchronisation above
+        A->allocs.erase(std::remove(A->allocs.begin(), A->allocs.end(), (void*)R.d), A->allocs.end());
+        (void)hipFree(R.d);
+    }
+    R = ResidentAnimation{d, n_frames, n_bones};
+    return CTL_OK;
+}
+
+CTL_API ctl_status ctl_scene_animate_frame(ctl_ctx* c, uint32_t anim, uint32_t animation, uint32_t frame, float lerp,
+                                           void* stream) {
+    if (!c) return CTL_ERR_INVALID;
+    if (!c->has_scene || !c->anim) { c->err = "scene_animate_frame: no scene uploaded"; return CTL_ERR_STATE; }
+    AnimState* A = c->anim;
+    if (anim >= A->meshes.size()) { c->err = "scene_animate_frame: animated mesh index out of range"; return CTL_ERR_INVALID; }
+    const AnimMeshPlan& P = A->meshes[anim];
+    if (animation >= P.resident.size() || !P.resident[animation].d) {
+        c->err = "scene_animate_frame: no resident animation (call ctl_scene_set_animation after the upload)";
+        return CTL_ERR_INVALID;
+    }
+    const ResidentAnimation& R = P.resident[animation];
+    if (frame >= R.n_frames) { c->err = "scene_animate_frame: frame index >= n_frames"; return CTL_ERR_INVALID; }
+    const ctl_status ok = animate_check(c, anim, R.n_bones, "scene_animate_frame");
+    if (ok != CTL_OK) return ok;
+    const uint32_t next = (frame + 1) % R.n_frames;   // AnimatedMesh.cpp:167
+    return animate_device(c, anim, R.d + 16ull * R.n_bones * frame, R.d + 16ull * R.n_bones * next, R.n_bones, lerp,
+                          reinterpret_cast<hipStream_t>(stream), "scene_animate_frame");
+}
+
+CTL_API ctl_status ctl_scene_animate_time(ctl_ctx* c, uint32_t anim, uint32_t animation, uint32_t frame_rate, float t,
+                                          void* stream) {
+    if (!c) return CTL_ERR_INVALID;
+    if (!c->has_scene || !c->anim) { c->err = "scene_animate_time: no scene uploaded"; return CTL_ERR_STATE; }
+    const AnimState* A = c->anim;
+    if (anim >= A->meshes.size() || animation >= A->meshes[anim].resident.size() ||
+        !A->meshes[anim].resident[animation].d) {
+        c->err = "scene_animate_time: no resident animation (call ctl_scene_set_animation after the upload)";
+        return CTL_ERR_INVALID;
+    }
+    uint32_t frame = 0;
+    float lerp = 0.0f;
+    if (ctl_animation_frame_index(frame_rate, A->meshes[anim].resident[animation].n_frames, t, &frame, &lerp) != CTL_OK)
+        return CTL_ERR_INVALID;
+    return ctl_scene_animate_frame(c, anim, animation, frame, lerp, stream);
+}
+
+static ctl_status animate_device(ctl_ctx* c, uint32_t anim, const float* b0, const float* b1, uint32_t n_bones,
+                                 float lerp, hipStream_t s, const char* what) {
+    AnimState* A = c->anim;
+    const AnimMeshPlan& P = A->meshes[anim];
     DevScene& S = c->scene;
     c->scene_epoch++;   // the geometry moves (render-ahead passes are dropped)
     const uint32_t nv = P.am.vertex_count, nt = P.am.tri_count;
     const uint32_t* tris = A->d_tris + 3ull * P.am.tri_first;
     if (nv) hipLaunchKernelGGL(anim_skin_kernel, dim3((nv + kAB - 1) / kAB), dim3(kAB), 34 * n_bones * sizeof(float), s,
-                               A->d_verts + P.am.vertex_first, nv, A->d_bones[0], A->d_bones[1], n_bones, lerp, A->d_P,
+                               A->d_verts + P.am.vertex_first, nv, b0, b1, n_bones, lerp, A->d_P,
                                A->d_N);
     if (nt) hipLaunchKernelGGL(anim_tri_kernel, dim3((nt + kAB - 1) / kAB), dim3(kAB), 0, s, tris, nt, A->d_P, A->d_N,
                                const_cast<ctl_triangle_data*>(S.tri_data) + P.km.triangle_offset);
@@ -1062,7 +1207,11 @@ CTL_API ctl_status ctl_scene_animate(ctl_ctx* c, uint32_t anim, const ctl_float4
         R.mesh_box = A->d_mesh_boxes + 6 * P.am.mesh;
         R.n_leaf = P.rb.n_leaf;
         R.n_nodes = P.rb.n_nodes;
-        hipLaunchKernelGGL(anim_leaf_kernel, dim3((P.rb.n_leaf + kAB - 1) / kAB), dim3(kAB), 0, s, R);
+        R.n_entries = P.n_entries;
+        if (P.rb.entry_woop)
+            hipLaunchKernelGGL(anim_entry_kernel, dim3((P.n_entries + kAB - 1) / kAB), dim3(kAB), 0, s, R);
+        else
+            hipLaunchKernelGGL(anim_leaf_kernel, dim3((P.rb.n_leaf + kAB - 1) / kAB), dim3(kAB), 0, s, R);
         hipLaunchKernelGGL(anim_rebuild_kernel, dim3((P.rb.n_leaf + kAB - 1) / kAB), dim3(kAB), 0, s, R);
         hipLaunchKernelGGL(anim_slot_kernel, dim3((P.rb.n_nodes + kAB - 1) / kAB), dim3(kAB), 0, s, R.bin, R.nrec, R.lrec,
                            R.leaf_of, R.leaf, P.rb.n_nodes);
@@ -1079,13 +1228,13 @@ CTL_API ctl_status ctl_scene_animate(ctl_ctx* c, uint32_t anim, const ctl_float4
                                nh - P.rb.wtop);
         }
     }
-    if (hipGetLastError() != hipSuccess) { c->err = "scene_animate: launch failed"; return CTL_ERR_HIP; }
+    if (hipGetLastError() != hipSuccess) { c->err = std::string(what) + ": launch failed"; return CTL_ERR_HIP; }
     // instances of the mesh, the instance tree, epsilon (DynamicScene::AnimateMesh invalidates the node)
     if (A->n_nodes) {
         std::vector<uint32_t> moved;
         for (uint32_t i = 0; i < A->n_nodes; i++)
             if (A->node_mesh[i] == P.am.mesh) moved.push_back(i);
-        const ctl_status r = scene_after_move(c, moved, s, "scene_animate");
+        const ctl_status r = scene_after_move(c, moved, s, what);
         if (r != CTL_OK) return r;
     }
     c->device_edited = true;

@@ -304,6 +304,80 @@ CTL_API ctl_status ctl_host_scene_set_bvh_builder(ctl_host_scene* s, uint32_t bu
     return CTL_OK;
 }
 
+CTL_API ctl_status ctl_host_scene_set_animated_bvh(ctl_host_scene* s, uint32_t mode) {
+    if (!s || mode > 1) { set_host_error("set_animated_bvh: invalid argument"); return CTL_ERR_INVALID; }
+    s->animated_bvh = mode;
+    return CTL_OK;
+}
+
+CTL_API int32_t ctl_host_scene_add_animation(ctl_host_scene* s, uint32_t mesh, const char* name, uint32_t frame_rate,
+                                             const ctl_float4x4* frames, uint32_t n_frames, uint32_t n_bones) {
+    if (!s || !frames || !name || mesh >= s->meshes.size() || !s->meshes[mesh].animated) {
+        set_host_error("add_animation: not an animated mesh");
+        return -1;
+    }
+    auto& M = s->meshes[mesh];
+    if (n_frames == 0 || n_bones == 0 || n_bones > 256 || M.max_bone >= n_bones) {
+        set_host_error("add_animation: need >= 1 frame of 1..256 bones covering the mesh's bone indices");
+        return -1;
+    }
+    if (strlen(name) > 127) { set_host_error("add_animation: name longer than 127 characters"); return -1; }
+    ctl_host_scene::Mesh::Animation a;
+    a.name = name;
+    a.frame_rate = frame_rate;
+    a.n_frames = n_frames;
+    a.n_bones = n_bones;
+    a.m.assign(frames, frames + (size_t)n_frames * n_bones);
+    M.animations.push_back(std::move(a));
+    return (int32_t)M.animations.size() - 1;
+}
+
+CTL_API int32_t ctl_host_scene_animation_count(ctl_host_scene* s, uint32_t mesh) {
+    if (!s || mesh >= s->meshes.size()) { set_host_error("animation_count: bad mesh index"); return -1; }
+    return (int32_t)s->meshes[mesh].animations.size();
+}
+
+CTL_API ctl_status ctl_host_scene_animation_info(ctl_host_scene* s, uint32_t mesh, uint32_t animation, char* name,
+                                                 uint32_t* frame_rate, uint32_t* n_frames, uint32_t* n_bones) {
+    if (!s || mesh >= s->meshes.size() || animation >= s->meshes[mesh].animations.size()) {
+        set_host_error("animation_info: bad mesh or animation index");
+        return CTL_ERR_INVALID;
+    }
+    const auto& a = s->meshes[mesh].animations[animation];
+    if (name) {
+        memset(name, 0, 128);
+        memcpy(name, a.name.data(), std::min<size_t>(a.name.size(), 127));
+    }
+    if (frame_rate) *frame_rate = a.frame_rate;
+    if (n_frames) *n_frames = a.n_frames;
+    if (n_bones) *n_bones = a.n_bones;
+    return CTL_OK;
+}
+
+CTL_API ctl_status ctl_host_scene_animation_frames(ctl_host_scene* s, uint32_t mesh, uint32_t animation,
+                                                   ctl_float4x4* out, uint64_t capacity) {
+    if (!s || !out || mesh >= s->meshes.size() || animation >= s->meshes[mesh].animations.size()) {
+        set_host_error("animation_frames: bad mesh or animation index");
+        return CTL_ERR_INVALID;
+    }
+    const auto& a = s->meshes[mesh].animations[animation];
+    if (capacity < a.m.size()) { set_host_error("animation_frames: buffer too small"); return CTL_ERR_INVALID; }
+    memcpy(out, a.m.data(), a.m.size() * sizeof(ctl_float4x4));
+    return CTL_OK;
+}
+
+CTL_API ctl_status ctl_animation_frame_index(uint32_t frame_rate, uint32_t n_frames, float t, uint32_t* frame,
+                                             float* lerp) {
+    if (n_frames == 0) { set_host_error("animation_frame_index: no frames"); return CTL_ERR_INVALID; }
+    const float a = (float)frame_rate * t;
+    if (lerp) *lerp = a - floorf(a);   // math::frac
+    if (frame) {
+        const uint32_t i = !(a >= 0.0f) ? 0u : a >= 4294967296.0f ? 0xffffffffu : (uint32_t)a;
+        *frame = i % n_frames;
+    }
+    return CTL_OK;
+}
+
 CTL_API ctl_status ctl_host_scene_compile(ctl_host_scene* s, uint32_t threads, ctl_scene_desc* out) {
     if (!s || !out) return CTL_ERR_INVALID;
     if (!s->has_camera) { set_host_error("compile: no camera"); return CTL_ERR_INVALID; }
@@ -358,7 +432,7 @@ CTL_API ctl_status ctl_host_scene_compile(ctl_host_scene* s, uint32_t threads, c
         bp.bins = s->sah_bins;
         bp.max_leaf = s->max_leaf;
         BvhOutput bo;
-        if (s->builder == CTL_BVH_SBVH && !M.animated) {
+        if (s->builder == CTL_BVH_SBVH && (!M.animated || s->animated_bvh)) {
             // the reference's SplitBVHBuilder (spatial splits inside the build)
             std::vector<float> tv((size_t)ntri * 9);
             parallel_for(ntri, threads, [&](uint64_t b, uint64_t e) {
@@ -373,7 +447,7 @@ CTL_API ctl_status ctl_host_scene_compile(ctl_host_scene* s, uint32_t threads, c
             sp.split_alpha = s->sbvh_alpha;
             sp.threads = threads;
             build_sbvh(tv.data(), ntri, sp, bo);
-        } else if (s->split_alpha > 0.0f && s->split_depth > 0 && !M.animated) {
+        } else if (s->split_alpha > 0.0f && s->split_depth > 0 && (!M.animated || s->animated_bvh)) {
             // references of large triangles split in space (ref_split.h)
             std::vector<float> tv((size_t)ntri * 9);
             parallel_for(ntri, threads, [&](uint64_t b, uint64_t e) {

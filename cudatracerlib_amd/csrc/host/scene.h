@@ -34,6 +34,13 @@ struct ctl_host_scene {
         bool animated = false;
         std::vector<ctl_anim_vertex> anim_v;
         uint32_t max_bone = 0;
+        // Animation (AnimatedMesh.h:35-55): n_frames x n_bones matrices, frame after frame
+        struct Animation {
+            std::string name;
+            uint32_t frame_rate = 0, n_frames = 0, n_bones = 0;
+            std::vector<ctl_float4x4> m;
+        };
+        std::vector<Animation> animations;
         uint32_t n_triangles() const { return precompiled ? (uint32_t)c_tri.size() : (uint32_t)(idx.size() / 3); }
     };
     struct Node { uint32_t mesh; bool has_xf; ctl::m44 xf; };
@@ -52,6 +59,7 @@ struct ctl_host_scene {
     uint32_t max_leaf = CTL_DEFAULT_MAX_LEAF;
     uint32_t builder = CTL_BVH_SBVH;   // ctl_host_scene_set_bvh_builder (default: the reference's SBVH)
     float sbvh_alpha = 1.0e-5f;
+    uint32_t animated_bvh = 0;         // ctl_host_scene_set_animated_bvh: 1 = skinned meshes take `builder` too
 
     // compiled arrays (owned)
     std::vector<ctl_triangle_data> tri_data;

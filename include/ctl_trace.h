@@ -45,7 +45,11 @@ extern "C" {
                                3: round 5 (ctl_occluded; CTL_SCENE_WIDE8 / CTL_ARRAY_W8_* / ctl_host_w8_tree
                                removed);
                                4: round 6 (CTL_PT_RENDER_AHEAD, CTL_ARRAY_CULL_BOUND; ctl_scene_animate /
-                               ctl_scene_set_transform rebuild trees with BVHRebuilder's rotations) */
+                               ctl_scene_set_transform rebuild trees with BVHRebuilder's rotations);
+                               still 4, symbols added only: animated .xmsh (ctl_host_scene_write_animated_xmsh,
+                               ctl_host_scene_set_animated_bvh, ctl_host_scene_add_animation / animation_*,
+                               ctl_animation_frame_index) and resident animations (ctl_scene_set_animation,
+                               ctl_scene_animate_frame, ctl_scene_animate_time) */
 
 #if defined(_WIN32)
 #define CTL_API __declspec(dllexport)
@@ -550,12 +554,41 @@ CTL_API ctl_status ctl_fb_reduce_all(ctl_ctx* const* ctxs, void* const* comms, c
  * TriangleData::setData) and TriIntersectorData (AnimProvider::setObject,
  * AnimatedMesh.cpp:113-117), refits its BVH boxes bottom-up, then the
  * instance boxes and the scene BVH, and recomputes the ray epsilon from the
- * new scene box (DynamicScene.cpp:587).  The refit keeps the compiled tree
- * (the reference's BVHRebuilder also rotates subtrees, BVHRebuilder.cpp:281-340;
- * traversal results do not depend on the tree).  Synchronises `stream` once
- * (the epsilon is a host-side kernel argument). */
+ * new scene box (DynamicScene.cpp:587).  The mesh tree is rebuilt as
+ * BVHRebuilder::Build(&p, true) leaves it: boxes bottom-up and the subtree
+ * rotations of recomputeNode (BVHRebuilder.cpp:281-340), so its shape carries
+ * over from call to call; the 4-wide copy keeps the upload's topology and is
+ * refit.  Synchronises `stream` once (the epsilon is a host-side kernel
+ * argument). */
 CTL_API ctl_status ctl_scene_animate(ctl_ctx* ctx, uint32_t anim, const ctl_float4x4* frame0,
                                      const ctl_float4x4* frame1, uint32_t n_bones, float lerp, void* stream);
+
+/* Animation `animation` of animated mesh `anim` kept on the device (the
+ * reference's AnimationFrame::m_sMatrices, AnimatedMesh.cpp:19-25): n_frames x
+ * n_bones row-major float4x4 in host memory, frame after frame, copied once.
+ * Replaces an earlier table of the same (anim, animation).  The tables live
+ * until the next ctl_scene_upload and are freed with the context.  Refused
+ * (CTL_ERR_INVALID) when a vertex of the mesh uses a bone index >= n_bones,
+ * when n_bones > 256 or n_frames == 0.  Synchronous. */
+CTL_API ctl_status ctl_scene_set_animation(ctl_ctx* ctx, uint32_t anim, uint32_t animation,
+                                           const ctl_float4x4* frames, uint32_t n_frames, uint32_t n_bones);
+/* AnimatedMesh::k_ComputeState(a_Anim, a_Frame, a_lerp) (AnimatedMesh.cpp:163-184):
+ * ctl_scene_animate between frames `frame` and (frame + 1) % n_frames of the
+ * resident table, without a host-to-device copy of matrices.  CTL_ERR_INVALID
+ * when the table was not set or frame >= n_frames. */
+CTL_API ctl_status ctl_scene_animate_frame(ctl_ctx* ctx, uint32_t anim, uint32_t animation, uint32_t frame,
+                                           float lerp, void* stream);
+/* The same at time t (seconds) of an animation played at `frame_rate`:
+ * ctl_animation_frame_index, then ctl_scene_animate_frame. */
+CTL_API ctl_status ctl_scene_animate_time(ctl_ctx* ctx, uint32_t anim, uint32_t animation, uint32_t frame_rate,
+                                          float t, void* stream);
+/* AnimatedMesh::ComputeFrameIndex (AnimatedMesh.h:84-91) in float arithmetic:
+ * a = (float)frame_rate * t, *lerp = a - floorf(a), *frame = (unsigned)a %
+ * n_frames.  An a below 0 (or NaN) counts as 0, one of 2^32 or more as
+ * 2^32 - 1 (the reference's conversion is undefined there).  Either output may
+ * be NULL.  CTL_ERR_INVALID when n_frames == 0. */
+CTL_API ctl_status ctl_animation_frame_index(uint32_t frame_rate, uint32_t n_frames, float t, uint32_t* frame,
+                                             float* lerp);
 
 /* Copies `count` elements from element `first` of a device scene array to
  * host memory (Stream<T>::CopyFromDevice, e.g. AnimatedMesh.cpp:178), for
@@ -829,15 +862,16 @@ CTL_API ctl_status ctl_host_scene_set_bvh_params(ctl_host_scene* s, float split_
  *   traversal): binned + splitting (alpha 0.1875, 64 bins, leaf 2, 41.7M
  *   references) 2250 Mrays/s; SBVH leaf 2: 2618 (26.6M references), leaf 1 / 3
  *   / 4 / 8: 2566 / 2560 / 2504 / 2345; split_alpha 1e-6 / 1e-4: 2642 / 2456.
- *   Skinned meshes always take the binned builder without splitting (refit). */
+ *   Skinned meshes take the binned builder without splitting unless
+ *   ctl_host_scene_set_animated_bvh(s, 1). */
 #define CTL_BVH_BINNED 0u
 #define CTL_BVH_SBVH 1u
 CTL_API ctl_status ctl_host_scene_set_bvh_builder(ctl_host_scene* s, uint32_t builder, float split_alpha);
 CTL_API ctl_status ctl_host_scene_compile(ctl_host_scene* s, uint32_t threads, ctl_scene_desc* out);
 
 /* Skinned mesh (AnimatedMesh, Engine/AnimatedMesh.h:71-110): compiled in its
- * rest pose (vertex positions as given; no reference splitting, so every
- * triangle has one BVH reference) and re-posed on the device by
+ * rest pose (vertex positions as given; by default no reference splitting, so
+ * every triangle has one BVH reference) and re-posed on the device by
  * ctl_scene_animate.  uvs: 2 floats per vertex or NULL; mat_index as
  * ctl_host_scene_add_mesh.  Area lights on animated meshes are refused at
  * compile (their ShapeSet would go stale).  Returns the mesh index or -1. */
@@ -848,8 +882,8 @@ CTL_API int32_t ctl_host_scene_add_animated_mesh(ctl_host_scene* s, const ctl_an
 
 /* Compiled meshes (.xmsh).  Replaces Mesh::Mesh(path, IInStream&, ...)
  * (Engine/Mesh.cpp:46-98) as called by DynamicScene::CreateNode(path)
- * (DynamicScene.cpp:270-345) on a static mesh file (leading u32
- * MeshCompileType 0; Animated files are refused): loads the box, MeshPartLights, TriangleData,
+ * (DynamicScene.cpp:270-345) on a mesh file (leading u32 MeshCompileType
+ * 0 Static or 1 Animated, see below): loads the box, MeshPartLights, TriangleData,
  * BVHNodeData, TriIntersectorData and TriIntersectorData2 arrays of the file
  * as they are (no rebuild).  Every node later created on the mesh gets one
  * area light per MeshPartLight, matched to a material by name
@@ -872,6 +906,48 @@ CTL_API int32_t ctl_host_scene_add_xmsh(ctl_host_scene* s, const void* data, uin
  * MeshPartLight per lit material.  out == NULL: only *size is set. */
 CTL_API ctl_status ctl_host_scene_write_xmsh(ctl_host_scene* s, uint32_t mesh, void* out, uint64_t capacity,
                                              uint64_t* size);
+
+/* Animated compiled meshes (leading MeshCompileType 1; AnimatedMesh::AnimatedMesh,
+ * AnimatedMesh.cpp:49-66).  ctl_host_scene_add_xmsh reads them: the static body,
+ * then e_KernelAnimatedMesh, the animations (frame rate, name, per frame its
+ * bone matrices), the AnimatedVertex records and one uint3 per TriangleData.
+ * The tree, entries and indices are kept as read (spatial-split duplicates and
+ * leaves of any length included) and rebuilt on the device by
+ * ctl_scene_animate*; the desc gets the mesh's ctl_anim_mesh record.  Checked
+ * beyond the static checks: the parent words (BVHRebuilder follows them),
+ * vertex indices < vertexCount, every frame of an animation holding the same
+ * 1..256 matrices and more than the largest bone index a vertex uses, at least
+ * one frame per animation, no MeshPartLight (area lights on animated meshes are
+ * not supported), no trailing bytes.
+ *
+ * ctl_host_scene_write_animated_xmsh writes animated mesh `mesh` of the last
+ * compile in that layout (out == NULL: only *size is set): the body of
+ * ctl_host_scene_write_xmsh under type 1, then the mesh's animations, vertices
+ * and triangles.  With ctl_host_scene_set_animated_bvh(s, 1) and the SBVH
+ * builder the file has the reference's tree shape (ConstructBVH on the rest
+ * pose, md5Compiler.cpp:94-111). */
+CTL_API ctl_status ctl_host_scene_write_animated_xmsh(ctl_host_scene* s, uint32_t mesh, void* out,
+                                                      uint64_t capacity, uint64_t* size);
+/* mode 0 (default): meshes of ctl_host_scene_add_animated_mesh compile with the
+ * binned builder and no splitting.  mode 1: with the scene's builder
+ * (ctl_host_scene_set_bvh_builder / set_bvh_params), so with CTL_BVH_SBVH
+ * spatial splits on the rest pose and leaves of up to max_leaf entries. */
+CTL_API ctl_status ctl_host_scene_set_animated_bvh(ctl_host_scene* s, uint32_t mode);
+/* Animations of an animated mesh (Animation, AnimatedMesh.h:35-55): n_frames x
+ * n_bones row-major float4x4, frame after frame; name up to 127 characters.
+ * n_bones must cover the mesh's bone indices (1..256).  Returns the animation's
+ * index in the mesh, or -1.  Animations read from a file are listed the same way. */
+CTL_API int32_t ctl_host_scene_add_animation(ctl_host_scene* s, uint32_t mesh, const char* name,
+                                             uint32_t frame_rate, const ctl_float4x4* frames, uint32_t n_frames,
+                                             uint32_t n_bones);
+/* number of animations of mesh `mesh` (0 for a static mesh), -1 on a bad index */
+CTL_API int32_t ctl_host_scene_animation_count(ctl_host_scene* s, uint32_t mesh);
+/* name: 128 bytes (NUL-terminated); any output may be NULL */
+CTL_API ctl_status ctl_host_scene_animation_info(ctl_host_scene* s, uint32_t mesh, uint32_t animation, char* name,
+                                                 uint32_t* frame_rate, uint32_t* n_frames, uint32_t* n_bones);
+/* all frames of an animation into out[n_frames * n_bones] */
+CTL_API ctl_status ctl_host_scene_animation_frames(ctl_host_scene* s, uint32_t mesh, uint32_t animation,
+                                                   ctl_float4x4* out, uint64_t capacity);
 CTL_API const char* ctl_host_last_error(void);
 
 /* Synthetic workloads of BASELINE.json (seed 0x5EED): 1 = C1 Cornell box

@@ -1,7 +1,10 @@
 """Animated-mesh throughput (ctl_scene_animate): a skinned grid
 of N x N quads (2 N^2 triangles, 16 bones, 4 influences per vertex) posed between
 two frames; prints one JSON line with ms per animate, per-stage algorithmic bytes
-and the resulting rates.  Run under `rocprofv3 --kernel-trace --stats` for the
+and the resulting rates.  --sbvh compiles the mesh as the reference compiles a
+skinned mesh (SBVH on the rest pose, leaves up to 8: duplicated references, long
+leaves); --resident keeps the two frames on the device and poses through
+ctl_scene_animate_frame.  Run under `rocprofv3 --kernel-trace --stats` for the
 per-kernel split (profiles/r01_anim_*)."""
 import argparse
 import json
@@ -45,49 +48,84 @@ def frames(bones, t):
     return np.stack(out)
 
 
+def make_scene(ctl, n, bones, sbvh):
+    """(host scene, desc, V, T) of the skinned grid; sbvh: set_animated_bvh(1), SBVH, max_leaf 8."""
+    V, N, BI, BW, T, UV = grid(n, bones)
+    s = ctl.HostScene()
+    if sbvh:
+        s.set_animated_bvh(1)
+        s.set_bvh_builder("sbvh", 1e-5)
+        s.set_bvh_params(0.0, 8, 0, 8)
+    s.add_animated_mesh(V, N, BI, BW, T, [ctl.diffuse_material(0.5, 0.5, 0.5)], uvs=UV)
+    s.add_animation(0, "pose", 24, np.stack([frames(bones, 0.0), frames(bones, 1.0)]))
+    s.add_node(0)
+    s.set_camera([0, 8, -20], [0, 0, 0], [0, 1, 0], 50, 64, 64)
+    return s, s.compile(), V, T
+
+
+def leaf_histogram(d):
+    """Leaves by entry count (index = entries per leaf) from the last-in-leaf flags."""
+    import ctypes as C
+    idx = np.ctypeslib.as_array(C.cast(d.tri_indices, C.POINTER(C.c_uint32)), shape=(int(d.n_tri_indices),))
+    ends = np.flatnonzero(idx & 1)
+    return np.bincount(np.diff(np.concatenate([[-1], ends]))).tolist()
+
+
+def time_calls(torch, call, iters):
+    """ms of each of `iters` calls, device events around each."""
+    ms = []
+    for k in range(iters):
+        e0 = torch.cuda.Event(enable_timing=True)
+        e1 = torch.cuda.Event(enable_timing=True)
+        e0.record()
+        call(k)
+        e1.record()
+        torch.cuda.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    return ms
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1024)
     ap.add_argument("--bones", type=int, default=16)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--binary", action="store_true", help="CTL_SCENE_BINARY_BVH: no 4-wide copy to refit")
+    ap.add_argument("--sbvh", action="store_true", help="reference-shaped tree: set_animated_bvh(1), SBVH, max_leaf 8")
+    ap.add_argument("--resident", action="store_true", help="frames kept on the device: ctl_scene_animate_frame")
     ap.add_argument("--shape", action="store_true", help="also report the tree's depth and the nodes one animate rotates")
     a = ap.parse_args()
     import ctypes as C
     import torch
     import cudatracerlib_amd as ctl
 
-    V, N, BI, BW, T, UV = grid(a.n, a.bones)
     t0 = time.perf_counter()
-    s = ctl.HostScene()
-    s.add_animated_mesh(V, N, BI, BW, T, [ctl.diffuse_material(0.5, 0.5, 0.5)], uvs=UV)
-    s.add_node(0)
-    s.set_camera([0, 8, -20], [0, 0, 0], [0, 1, 0], 50, 64, 64)
-    d = s.compile()
+    s, d, V, T = make_scene(ctl, a.n, a.bones, a.sbvh)
     if a.binary:
         d.flags |= ctl.CTL_SCENE_BINARY_BVH
     t_build = time.perf_counter() - t0
     pt = ctl.PathTracer(0)
     pt.upload_scene(d)
     f0, f1 = frames(a.bones, 0.0), frames(a.bones, 1.0)
+    if a.resident:
+        pt.upload_animations(s)
+
+    def pose(lerp):
+        if a.resident:
+            pt.animate_frame(0, 0, 0, lerp)
+        else:
+            pt.animate(0, f0, f1, lerp)
+
     for _ in range(3):
-        pt.animate(0, f0, f1, 0.5)
+        pose(0.5)
     torch.cuda.synchronize()
-    ms = []
-    for k in range(a.iters):
-        e0 = torch.cuda.Event(enable_timing=True)
-        e1 = torch.cuda.Event(enable_timing=True)
-        e0.record()
-        pt.animate(0, f0, f1, (k + 0.5) / a.iters)
-        e1.record()
-        torch.cuda.synchronize()
-        ms.append(e0.elapsed_time(e1))
+    ms = time_calls(torch, lambda k: pose((k + 0.5) / a.iters), a.iters)
     nv, nt, ne, nn = V.shape[0], T.shape[0], int(d.n_woop_tris), int(d.n_bvh_nodes)
     shape = {}
     if a.shape:
         from cudatracerlib_amd import _abi
         before = pt.read_array(_abi.CTL_ARRAY_BVH_NODES, 0, nn, np.int32, 16)
-        pt.animate(0, f0, f1, 0.37)
+        pose(0.37)
         after = pt.read_array(_abi.CTL_ARRAY_BVH_NODES, 0, nn, np.int32, 16)
         shape["nodes_with_new_children"] = int(np.any(before[:, 12:14] != after[:, 12:14], axis=1).sum())
         kids = after[:, 12:14]
@@ -107,12 +145,15 @@ def main():
     per = sorted(ms)[len(ms) // 2]
     print(json.dumps({
         "workload": f"skinned grid {a.n}x{a.n} quads: {nv} vertices, {nt} triangles, {a.bones} bones, 4 influences"
-                    + (", binary tree only" if a.binary else ""),
+                    + (", binary tree only" if a.binary else "") + (", SBVH leaves <= 8" if a.sbvh else "")
+                    + (", resident frames" if a.resident else ""),
         "ms_per_animate_median": round(per, 4), "ms_min": round(min(ms), 4),
         "mtris_per_s": round(nt / per / 1e3, 1),
         "alg_bytes_per_animate": int(alg), "alg_GBps": round(alg / (per * 1e-3) / 1e9, 1),
-        "bvh_nodes": nn, "scene_build_s": round(t_build, 2),
-        "note": "includes the epsilon readback (one stream sync) and 2 x 1 KB bone uploads",
+        "bvh_nodes": nn, "entries": ne, "entries_per_triangle": round(ne / nt, 4),
+        "leaves_by_entries": leaf_histogram(d), "scene_build_s": round(t_build, 2),
+        "note": "includes the epsilon readback (one stream sync)"
+                + ("" if a.resident else " and 2 x 1 KB bone uploads"),
         **shape,
     }), flush=True)
     pt.close()
