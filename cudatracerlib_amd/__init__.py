@@ -12,6 +12,8 @@ of the reference's surface for that path:
   UpdateKernel / KernelDynamicScene upload                  Tracer.upload_scene
   __internal__IntersectBuffers (TraceHelper.cu:736-746)     Tracer.intersect_buffers
   PathTracer::DoPass (Kernel/Tracer.h:209-248)              PathTracer.do_pass
+  DoPass with an IBlockSampler (Tracer.h:233-237,264-289)   PathTracer.do_pass_adaptive
+  VarianceBlockSampler (Kernel/BlockSampler)                BlockSampler
   k_getNumRaysTraced (TraceHelper.cu:309-314)               Tracer.rays_traced
 
 Device memory, streams and torch.distributed come from PyTorch; no torch type
@@ -29,7 +31,7 @@ from ._abi import (PTParams, WptParams, PrimParams, SceneDesc, Material, Pixel, 
                    CTL_BSDF_DIFFUSE, CTL_EDIFFUSE_REFLECTION, CTL_PT_MEGAKERNEL, CTL_PT_WAVEFRONT, CTL_PT_RENDER_AHEAD,
                    CTL_COMM_ID_BYTES)
 
-__all__ = ["HostScene", "Tracer", "PathTracer", "WavefrontPathTracer", "PrimTracer", "PrimParams", "WptParams", "PTParams", "SceneDesc", "Material", "Pixel", "Ray", "Hit",
+__all__ = ["HostScene", "Tracer", "PathTracer", "BlockSampler", "BLOCK_INFO_DTYPE", "WavefrontPathTracer", "PrimTracer", "PrimParams", "WptParams", "PTParams", "SceneDesc", "Material", "Pixel", "Ray", "Hit",
            "roughdielectric_material", "set_alpha_map", "comm_unique_id", "comm_init_rank", "comm_init_all",
            "comm_destroy",
            "CTL_SCENE_HALF_HOST_QUIRK", "CTL_SCENE_BINARY_BVH", "CTL_PT_MEGAKERNEL", "CTL_PT_WAVEFRONT", "CTL_PT_RENDER_AHEAD", "lib", "diffuse_material"]
@@ -351,6 +353,88 @@ def host_wide_trees(desc):
     return mesh, wbase, scene
 
 
+# ctl_block_info (VarianceBlockSampler::TmpBlockInfo) as a numpy record
+BLOCK_INFO_DTYPE = np.dtype([("block_var_i", np.float32), ("num_pixels_var", np.uint32), ("block_e_i", np.float32),
+                             ("block_e_i2", np.float32), ("num_pixels_e", np.uint32)])
+
+
+class BlockSampler:
+    """IBlockSampler (Kernel/BlockSampler/IBlockSampler.h): which blocks the next pass
+    renders.  type "uniform" (UniformBlockSampler) or "variance" (VarianceBlockSampler:
+    uniform for 10 passes, then the noisiest N / frac_weighted blocks plus every
+    frac_deterministic-th one, rotating).  Host only, no GPU."""
+
+    def __init__(self, width, height, tile_size=64, type="variance"):
+        self._L = lib()
+        t = {"uniform": _abi.CTL_BST_UNIFORM, "variance": _abi.CTL_BST_VARIANCE}.get(type, type)
+        self._h = self._L.ctl_block_sampler_create(int(width), int(height), int(tile_size), int(t))
+        if not self._h:
+            self._h = None
+            _check(1, None, "ctl_block_sampler_create")
+        self.width, self.height, self.tile_size = int(width), int(height), int(tile_size)
+        self.blocks_x = -(-self.width // self.tile_size)
+        self.blocks_y = -(-self.height // self.tile_size)
+        self.num_blocks = self.blocks_x * self.blocks_y
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.ctl_block_sampler_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def start_new_rendering(self):
+        _check(self._L.ctl_block_sampler_start_new_rendering(self._h), None, "ctl_block_sampler_start_new_rendering")
+
+    def set_fractions(self, frac_deterministic=2, frac_weighted=4):
+        _check(self._L.ctl_block_sampler_set_fractions(self._h, int(frac_deterministic), int(frac_weighted)), None,
+               "ctl_block_sampler_set_fractions")
+
+    def set_user_weight(self, bx, by, w):
+        _check(self._L.ctl_block_sampler_set_user_weight(self._h, int(bx), int(by), float(w)), None,
+               "ctl_block_sampler_set_user_weight")
+
+    def blocks(self):
+        """IterateBlocks: the block ids of the next pass, in order (uint32 array)."""
+        n = C.c_uint32(0)
+        out = np.zeros(2 * self.num_blocks, np.uint32)   # a block is listed twice at most (once per half)
+        _check(self._L.ctl_block_sampler_blocks(self._h, out.ctypes.data, out.size, C.byref(n)), None,
+               "ctl_block_sampler_blocks")
+        return out[:n.value].copy()
+
+    def tile_samples(self):
+        """The next pass's list as one uint8 count per block (variance_add_pass's tile_samples)."""
+        out = np.zeros(self.num_blocks, np.uint8)
+        _check(self._L.ctl_block_sampler_tile_samples(self._h, out.ctypes.data), None,
+               "ctl_block_sampler_tile_samples")
+        return out
+
+    def add_pass(self, info=None):
+        """AddPass: `info` = the finished pass's block statistics (BLOCK_INFO_DTYPE records or
+        anything of that layout, one per block); the uniform sampler needs none."""
+        if info is None:
+            _check(self._L.ctl_block_sampler_add_pass(self._h, None, 0), None, "ctl_block_sampler_add_pass")
+            return
+        a = np.ascontiguousarray(info)
+        if a.dtype != BLOCK_INFO_DTYPE:
+            a = np.ascontiguousarray(a).view(np.uint8).reshape(-1).view(BLOCK_INFO_DTYPE)
+        _check(self._L.ctl_block_sampler_add_pass(self._h, a.ctypes.data, a.size), None, "ctl_block_sampler_add_pass")
+
+    def weights(self):
+        out = np.zeros(self.num_blocks, np.float32)
+        _check(self._L.ctl_block_sampler_weights(self._h, out.ctypes.data), None, "ctl_block_sampler_weights")
+        return out
+
+    def passes_done(self):
+        out = np.zeros(self.num_blocks, np.uint32)
+        _check(self._L.ctl_block_sampler_passes_done(self._h, out.ctypes.data), None, "ctl_block_sampler_passes_done")
+        return out
+
+
 class Tracer:
     """Per-GPU traversal context (InitializeKernel/UpdateKernel/IntersectBuffers)."""
 
@@ -492,6 +576,13 @@ class Tracer:
         _check(self._L.ctl_variance_stats(self._ctx, var_ptr, int(n), err_ptr, variance_ptr, average_ptr, stream),
                self._ctx, "ctl_variance_stats")
 
+    def block_stats(self, var_ptr, width, height, tile_size, out_ptr, stream=0):
+        """VarianceBlockSampler's updateInfo (ctl_block_stats): the per-block sums of the pixel
+        variances and averages into device ctl_block_info[ceil(w/ts) * ceil(h/ts)] (20 B each,
+        BLOCK_INFO_DTYPE), summed in a fixed order -- bitwise reproducible."""
+        _check(self._L.ctl_block_stats(self._ctx, var_ptr, int(width), int(height), int(tile_size), out_ptr, stream),
+               self._ctx, "ctl_block_stats")
+
     def sync(self, stream=0):
         """Wait for the stream; raises CTLError if a traversal stack overflowed since the last reset_rays."""
         _check(self._L.ctl_sync(self._ctx, stream), self._ctx, "ctl_sync")
@@ -583,6 +674,39 @@ class PathTracer(Tracer):
         _check(self._L.ctl_camera_rays(self._ctx, C.byref(self.params), rays_ptr, int(capacity), C.byref(n), stream),
                self._ctx, "ctl_camera_rays")
         return n.value
+
+    def render_pass_blocks(self, fb_ptr, blocks, stream=0):
+        """One pass over the listed blocks (ctl_render_pass_blocks) with the sampler tables
+        already generated: a full pass masked to `blocks` (row-major block ids over
+        params.tile_size blocks; an id listed m times is added m times)."""
+        b = np.ascontiguousarray(blocks, dtype=np.uint32).reshape(-1)
+        _check(self._L.ctl_render_pass_blocks(self._ctx, C.byref(self.params), b.ctypes.data if b.size else None,
+                                              b.size, fb_ptr, stream), self._ctx, "ctl_render_pass_blocks")
+
+    def do_pass_adaptive(self, fb_ptr, var_ptr, sampler, pass_index, stream=0):
+        """Tracer<true>::DoPass with an IBlockSampler (Kernel/Tracer.h:209-248): the sampler
+        tables of `pass_index`, a pass over sampler.blocks(), PixelVarianceBuffer::AddPass with
+        the sampler's counts (splat scale 1 / passes), the per-block statistics, their
+        read-back (20 B per block) and sampler.add_pass.  fb_ptr / var_ptr: device
+        PixelData[w*h] / PixelVarianceInfo[w*h] (zeroed before the first pass).
+        Returns the list that was rendered."""
+        import torch
+        if sampler.tile_size != (self.params.tile_size or 64):
+            raise ValueError("do_pass_adaptive: the sampler's tile_size differs from params.tile_size")
+        w, h, n = sampler.width, sampler.height, sampler.num_blocks
+        blocks = sampler.blocks()
+        counts = sampler.tile_samples()
+        self.generate_samples(pass_index, stream)
+        self.render_pass_blocks(fb_ptr, blocks, stream)
+        self.variance_add_pass(fb_ptr, w, h, counts, var_ptr, splat_scale=1.0 / (pass_index + 1),
+                               tile_size=sampler.tile_size, stream=stream)
+        buf = getattr(self, "_block_info", None)
+        if buf is None or buf.numel() < 5 * n:
+            buf = self._block_info = torch.empty(5 * n, dtype=torch.int32, device=torch.device("cuda", self.device))
+        self.block_stats(var_ptr, w, h, sampler.tile_size, buf.data_ptr(), stream)
+        self.sync(stream)
+        sampler.add_pass(buf[:5 * n].cpu().numpy().view(BLOCK_INFO_DTYPE))
+        return blocks
 
     def pass_stats(self, fb_ptr, pass_index, stream=0):
         self.generate_samples(pass_index, stream)

@@ -176,6 +176,14 @@ class PixelVariance(C.Structure):    # PixelVarianceInfo, 44 B
                 ("weight", C.c_float), ("sum_x", C.c_float), ("sum_x2", C.c_float), ("num_samples_var", C.c_int32)]
 
 
+class BlockInfo(C.Structure):        # VarianceBlockSampler::TmpBlockInfo, 20 B
+    _fields_ = [("block_var_i", C.c_float), ("num_pixels_var", C.c_uint32), ("block_e_i", C.c_float),
+                ("block_e_i2", C.c_float), ("num_pixels_e", C.c_uint32)]
+
+
+CTL_BST_UNIFORM, CTL_BST_VARIANCE = 0, 1   # ctl_block_sampler_create types
+
+
 class PTParams(C.Structure):
     _fields_ = [("direct", C.c_int32), ("max_path_length", C.c_int32), ("rr_start_depth", C.c_int32),
                 ("shadow_any_hit", C.c_int32), ("tile_size", C.c_uint32), ("num_ranks", C.c_uint32),
@@ -277,6 +285,18 @@ SYMBOLS = [
     ("ctl_scene_animate_time", C.c_int32, [_vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, _vp]),
     ("ctl_host_last_error", C.c_char_p, []),
     ("ctl_host_scene_generate", C.c_int32, [_vp, C.c_int32, C.c_double, C.c_uint32, C.c_uint32]),
+    ("ctl_render_pass_blocks", C.c_int32, [_vp, C.POINTER(PTParams), _vp, C.c_uint32, _vp, _vp]),
+    ("ctl_block_stats", C.c_int32, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp]),
+    ("ctl_block_sampler_create", _vp, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
+    ("ctl_block_sampler_destroy", None, [_vp]),
+    ("ctl_block_sampler_start_new_rendering", C.c_int32, [_vp]),
+    ("ctl_block_sampler_set_fractions", C.c_int32, [_vp, C.c_uint32, C.c_uint32]),
+    ("ctl_block_sampler_set_user_weight", C.c_int32, [_vp, C.c_uint32, C.c_uint32, C.c_float]),
+    ("ctl_block_sampler_blocks", C.c_int32, [_vp, _vp, C.c_uint32, C.POINTER(C.c_uint32)]),
+    ("ctl_block_sampler_tile_samples", C.c_int32, [_vp, _vp]),
+    ("ctl_block_sampler_add_pass", C.c_int32, [_vp, _vp, C.c_uint32]),
+    ("ctl_block_sampler_weights", C.c_int32, [_vp, _vp]),
+    ("ctl_block_sampler_passes_done", C.c_int32, [_vp, _vp]),
 ]
 
 _lib = None

@@ -230,6 +230,23 @@ __device__ __forceinline__ void store_sample(const PathParams& P, const SampleSl
     S.s[(size_t)ps * S.per_pass + kk] = make_float4(col.x, col.y, col.z, code);
 }
 
+// store_sample in two halves, for a kernel that knows the pixel only when the path
+// starts (the block-list pass, whose item -> pixel map goes through tables): the
+// landing code from the pixel and its jittered position, and the store from the
+// code once the radiance is known.  Together they write what store_sample writes.
+__device__ __forceinline__ uint32_t landing_code(const PathParams& P, uint32_t px, uint32_t py, f2 pX) {
+    const int x = (int)floorf(pX.x), y = (int)floorf(pX.y);
+    const int dx = x - (int)px, dy = y - (int)py;
+    const bool in = x >= 0 && x < (int)P.width && y >= 0 && y < (int)P.height && (dx | dy) >= 0 && dx <= 1 && dy <= 1;
+    return in ? (uint32_t)(1 + dx + 2 * dy) : 0u;
+}
+__device__ __forceinline__ void store_sample_coded(const SampleSlots& S, uint32_t k, uint32_t code, spec col) {
+    col.x = tmax(0.0f, col.x); col.y = tmax(0.0f, col.y); col.z = tmax(0.0f, col.z);
+    const bool valid = !(isnan(col.x) || isnan(col.y) || isnan(col.z)) && isfinite(col.x) && isfinite(col.y) &&
+                       isfinite(col.z) && col.x >= 0.0f && col.y >= 0.0f && col.z >= 0.0f;
+    S.s[k] = make_float4(col.x, col.y, col.z, valid ? (float)code : 0.0f);
+}
+
 // Apron item g keeps its path only when the sample lands inside its tile.
 __device__ __forceinline__ bool apron_keep(const PathParams& P, uint64_t g, f2 pX) {
     if (!P.apron || g < P.owned_items) return true;
@@ -267,6 +284,94 @@ __device__ __forceinline__ bool source_item(const PathParams& P, uint32_t sx, ui
     k = P.owned_items + (tile / P.num_ranks) * P.apron + i;
     return true;
 }
+
+// Ownership policies of the persistent path kernel and the fold: which tiles a
+// pass renders and where a pixel's work item lives.
+//   OwnModulo  tile % num_ranks == rank, slot tile / num_ranks (the functions
+//              above; `T` unused), every pass but a block-list one;
+//   OwnList    the blocks of a list (ctl_render_pass_blocks), through device
+//              tables at T (own_list_words words): slot -> the block's pixel
+//              origin (x0, y0), block -> slot (kUnlisted when absent), slot ->
+//              multiplicity.
+// A list pass numbers its work items like an N-rank pass: owned_items pixels of
+// the listed blocks by slot, then apron items per slot (P.apron = 2 ts + 1)
+// for the samples that stray in from unlisted neighbours; an apron item whose
+// pixel lies in a listed block is skipped (that block's own item covers it).
+// The table lookups are per tile, so an 8x8 pixel group reads one entry; a
+// wave's refilled lanes hold non-consecutive items, so they are per-lane loads.
+// The origin table spares the refill the two divisions by tiles_x.
+constexpr uint32_t kUnlisted = 0xffffffffu;
+struct OwnModulo {
+    static __device__ __forceinline__ bool work_pixel(const PathParams& P, const uint32_t*, uint64_t g, uint32_t& px,
+                                                      uint32_t& py) {
+        return ctl::work_pixel(P, g, px, py);
+    }
+    static __device__ __forceinline__ bool apron_keep(const PathParams& P, const uint32_t*, uint64_t g, f2 pX) {
+        return ctl::apron_keep(P, g, pX);
+    }
+};
+struct OwnList {
+    // table layout in words, nt = num_tiles: [0, 2 nt) origins, [2 nt, 3 nt) block -> slot, [3 nt, 4 nt) multiplicity
+    static __host__ __device__ constexpr size_t words(uint32_t nt) { return 4 * (size_t)nt; }
+    static __host__ __device__ constexpr size_t slot_of_off(uint32_t nt) { return 2 * (size_t)nt; }
+    static __host__ __device__ constexpr size_t mult_off(uint32_t nt) { return 3 * (size_t)nt; }
+    // slot j < listed blocks <= num_tiles (the host bounds the work items)
+    static __device__ __forceinline__ uint2 origin(const uint32_t* T, uint32_t j) {
+        return reinterpret_cast<const uint2*>(T)[j];
+    }
+    static __device__ __forceinline__ uint32_t slot_of(const PathParams& P, const uint32_t* T, uint32_t x, uint32_t y) {
+        return T[slot_of_off(P.num_tiles) + (y / P.tile_size) * P.tiles_x + x / P.tile_size];   // x < width, y < height
+    }
+    // Branch-free, both table reads unconditional (indices clamped into the tables):
+    // the refill stays one straight-line block, as the modulo form's is -- with the
+    // reads under branches the FULL kernels spill 9 more VGPRs
+    // (profiles/adaptive_kernel_resources.txt).
+    static __device__ __forceinline__ bool work_pixel(const PathParams& P, const uint32_t* T, uint32_t g, uint32_t& px,
+                                                      uint32_t& py) {
+        const uint32_t ts = P.tile_size;
+        const bool ap = g >= P.owned_items;
+        const uint32_t a = g - P.owned_items;                       // apron item (when ap)
+        const uint32_t j = ap ? a / P.apron : g / (ts * ts);        // slot < listed blocks either way
+        const uint2 o = origin(T, j);
+        // the slot's own pixel
+        const uint32_t w = g % (ts * ts), groupsPerRow = ts / 8, grp = w / 64, lane = w % 64;
+        const uint32_t ox = o.x + (grp % groupsPerRow) * 8 + lane % 8, oy = o.y + (grp / groupsPerRow) * 8 + lane / 8;
+        // the slot's apron pixel: left column, top row, corner (wraps below 0 are caught by the bounds)
+        const uint32_t i = a % P.apron;
+        const uint32_t ax = i < ts ? o.x - 1 : i < 2 * ts ? o.x + (i - ts) : o.x - 1;
+        const uint32_t ay = i < ts ? o.y + i : o.y - 1;
+        const bool ain = ax < P.width && ay < P.height;            // o.x - 1 with o.x == 0 is 2^32 - 1: outside
+        const uint32_t t2 = ap && ain ? (ay / ts) * P.tiles_x + ax / ts : 0u;
+        const uint32_t s2 = T[slot_of_off(P.num_tiles) + t2];
+        px = ap ? ax : ox;
+        py = ap ? ay : oy;
+        // a listed block's pixel has its own item
+        return ap ? ain && s2 == kUnlisted : ox < P.width && oy < P.height;
+    }
+    static __device__ __forceinline__ bool apron_keep(const PathParams& P, const uint32_t* T, uint32_t g, f2 pX) {
+        if (g < P.owned_items) return true;
+        const uint2 o = origin(T, (g - P.owned_items) / P.apron);
+        const float lx = floorf(pX.x), ly = floorf(pX.y);
+        return lx >= (float)o.x && lx < (float)(o.x + P.tile_size) && ly >= (float)o.y && ly < (float)(o.y + P.tile_size);
+    }
+    // Work item of source pixel (sx, sy) for a target pixel of the listed block in
+    // slot `tslot` at (x0, y0): its own item when its block is listed, else the
+    // target block's apron item.
+    static __device__ __forceinline__ uint32_t source_item(const PathParams& P, const uint32_t* T, uint32_t sx,
+                                                           uint32_t sy, uint32_t tslot, uint32_t x0, uint32_t y0) {
+        const uint32_t ts = P.tile_size;
+        const uint32_t slot = slot_of(P, T, sx, sy);
+        if (slot != kUnlisted) {
+            const uint32_t xx = sx % ts, yy = sy % ts;
+            return slot * ts * ts + ((yy / 8) * (ts / 8) + xx / 8) * 64 + (yy % 8) * 8 + xx % 8;
+        }
+        uint32_t i;
+        if (sx + 1 == x0 && sy + 1 == y0) i = 2 * ts;
+        else if (sx + 1 == x0) i = sy - y0;
+        else i = ts + (sx - x0);
+        return P.owned_items + tslot * P.apron + i;
+    }
+};
 
 // Loop-carried variables of PathTrace<true> (PathTracer.cu:10-33).  wo and
 // brdf_pdf persist: diffuse_sample leaves them untouched when it rejects a
@@ -640,6 +745,16 @@ struct ctl_ctx {
     int stack_bound = 0;                        // worst-case traversal stack of the uploaded scene
     uint8_t* d_tile_flags = nullptr;            // PixelVarianceBuffer block flags
     size_t tile_flags_cap = 0;
+    // ctl_render_pass_blocks: the OwnList tables (OwnList::words), filled in one half
+    // of the pinned staging buffer and uploaded stream-ordered.  The halves alternate
+    // and block_ev[h] marks half h's last upload, so the host waits only for the
+    // upload of two calls ago and a caller can queue list passes without stalling.
+    uint32_t* d_block_tbl = nullptr;
+    uint32_t* h_block_tbl = nullptr;            // 2 x OwnList::words(block_tbl_cap)
+    size_t block_tbl_cap = 0;                   // tiles the copies are allocated for
+    hipEvent_t block_ev[2] = {nullptr, nullptr};
+    bool block_ev_set[2] = {false, false};      // block_ev[h] has been recorded
+    uint32_t block_half = 0;                    // the half the next call fills
     uint32_t* d_powers = nullptr;               // XORWOW step powers for sampler_kernel
     ctl::WfState wf{};
     std::vector<void*> wf_allocs;

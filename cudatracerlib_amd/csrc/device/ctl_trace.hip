@@ -10,6 +10,9 @@
 //                      (both: sensor ray + PathTrace<true> + AddSample;
 //                       pathKernel2 / PathTrace, Integrators/PathTracer.cu:10-113,182-194;
 //                       Image::AddSample, Engine/Image.cu:22-44)
+//   fold_blocks_kernel the sample fold of a block-list pass (ctl_render_pass_blocks:
+//                      path_kernel_persistent_blocks, the persistent loop with the
+//                      OwnList ownership policy, common.h)
 //   sampler_kernel     SequenceSamplerData tables of a pass (Sampler.cu, CudaRandom.cu)
 // The wavefront schedule lives in wavefront.hip.
 #include <hip/hip_runtime.h>
@@ -71,6 +74,8 @@ namespace {
 // block: 4 blocks per CU, i.e. the 4 waves/SIMD the VGPR budget targets.
 // Lean kernel VGPR spills 36 -> 11; C3 2983 -> 3219 Mrays/s (profiles/r03_park_slack_ab.txt).
 constexpr int kParkWords = 23;
+// a block-list pass packs (work item, landing code 0..4) into the parked work item word
+constexpr uint32_t kListItemBits = 29, kListItemMask = (1u << kListItemBits) - 1;
 struct Park {
     int tid;
     __device__ __forceinline__ void put(int w, float x) const {
@@ -353,171 +358,34 @@ __global__ __launch_bounds__(kBlock) void path_kernel(DevScene S_arg, PathParams
 //    pending ray are loop-carried, keeping the register peak low.
 // Work items are independent (own sampler index, own sample slot), so the
 // framebuffer is bit-identical to path_kernel's.
+// The loop is persistent_loop.h, the body of two kernel templates so that the
+// default kernels keep their names and code: path_kernel_persistent (ownership
+// tile % num_ranks == rank) and path_kernel_persistent_blocks (the blocks of a
+// list, ctl_render_pass_blocks).
+#define CTL_PERSIST_KERNEL_ATTRS \
+    __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(SINGLE ? (FULL ? CTL_PERSIST_WAVES_FULL : CTL_PERSIST_WAVES) : 2)))
+
 template <bool STATS, bool SINGLE, int WIDE, int FULL>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(SINGLE ? (FULL ? CTL_PERSIST_WAVES_FULL : CTL_PERSIST_WAVES) : 2))) void path_kernel_persistent(DevScene S_arg, PathParams P_arg, const float* s1,
-                                                                 const float2* s2, uint64_t items,
-                                                                 unsigned long long* cursor, unsigned long long* counters,
-                                                                 SampleSlots PS, uint32_t tbl) {
-    // Work item k renders pass slot k / PS.per_pass (sampler tables at
-    // s1/s2 + slot * tbl) of work item k % PS.per_pass; every finished sample
-    // goes to its own slot, folded into the framebuffer afterwards (store_sample).
-    // The scene and pass records are read in place from the kernel-argument
-    // segment (scalar loads at their uses) rather than held in SGPRs for the
-    // kernel's lifetime: 100+ live SGPRs spilled into VGPR lanes and from
-    // there to scratch.  C3 3184 -> 3310, C5 1662 -> 1772 Mrays/s; VGPR spills
-    // lean 10 -> 0, full 98 -> 40 (profiles/r03_park_slack_ab.txt).
-    const DevScene& S = kernarg_ref<DevScene>(S_arg, 0);
-    const PathParams& P = kernarg_ref<PathParams>(P_arg, kernarg_next<DevScene, PathParams>(0));
-    CTL_LANE_STACK(st);
-    SamplerDev rng{s1, s2, P.nseq, P.len, 0, 0, 0, 0};
-    // work item of the lane's path (pass slot * PS.per_pass + item), parked in
-    // LDS for the path's lifetime instead of holding a VGPR through the traces
-    int* pkw = ctl_lds_stack + kPathWordOff + threadIdx.x;
-    const Park park{(int)threadIdx.x};
-    auto split = [&](uint32_t k, uint32_t& ps, uint32_t& kk) { PS.split(k, ps, kk); };
-    PathVars v;
-    ShadowReq sh;
-    sh.valid = false;
-    sh.dist = 0.0f;
-    TraceStats ts{0, 0, 0};
-    uint32_t rays = 0;
-    bool active = false, exhausted = false, shadowPhase = false, ending = false, ok = true;
-#ifdef CTL_PROFILE_TRACE
-    long long prof_trace = 0;
-    const long long prof_start = wall_clock64();
-#endif
-    const bool shadowAny = P.shadow_any_hit != 0;
-    const int lane = threadIdx.x & 63;
-    while (true) {
-        const bool need = !active && !exhausted;
-        const uint64_t mask = __ballot(need);
-        if (mask) {
-            const int leader = __ffsll((unsigned long long)mask) - 1;
-            unsigned long long base = 0;
-            if (lane == leader) base = atomicAdd(cursor, (unsigned long long)__popcll(mask));
-            base = __shfl(base, leader);
-            if (need) {
-                const uint64_t k64 = base + (uint64_t)lanes_below(mask);
-                if (k64 >= items) {
-                    exhausted = true;
-                } else {
-                    const uint32_t k = (uint32_t)k64;   // items < 2^32 (checked on the host)
-                    uint32_t px, py, ps, kk;
-                    split(k, ps, kk);
-                    // FULL: the pass record read through an opaque pointer here, so the
-                    // divisions by its fields keep their reciprocals local to the refill
-                    // (hoisted, they held VGPRs the FULL kernel spilled for its lifetime;
-                    // the lean kernel has the registers and keeps them hoisted)
-                    const PathParams& Pw = FULL ? *opaque_ptr(&P) : P;
-                    if (work_pixel(Pw, kk, px, py)) {
-                        const uint32_t idx = py * Pw.width + px;
-                        // the pass slot's tables start ps * tbl elements in: folded into
-                        // the two sequence offsets so the table bases stay kernel-uniform
-                        rng.a = idx % Pw.nseq + ps * tbl; rng.b = (idx / Pw.nseq) % Pw.nseq + ps * tbl;
-                        rng.d1 = 0; rng.d2 = 0;
-                        *pkw = (int)k;
-                        f3 o, dw;
-                        const f2 pX = primary_ray(S, rng, px, py, o, dw);
-                        v.begin(pX, o, dw);
-                        shadowPhase = false;
-                        ending = false;
-                        // loop head of PathTrace: `while (depth++ < MaxPathLength)`
-                        if (!apron_keep(Pw, kk, pX)) PS.s[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-                        else if (v.depth++ < P.max_path_length) active = true;
-                        else store_sample(P, PS, ps, kk, px, py, v.pX, mk3s(1.0f) * v.cl);
-                        if (active) park.begin(v, rng);
-                    } else {
-                        PS.s[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);   // work item outside the image: no sample
-                    }
-                }
-            }
-        }
-        if (!__any(active)) {
-            if (__all(exhausted)) break;
-            continue;
-        }
-        if (active) {
-            HitRec h;
-            h.t = (shadowPhase && shadowAny) ? sh.dist - S.ray_eps : FLT_MAX;
-            h.u = h.v = 0.0f; h.tri = 0xffffffffu; h.node = 0xffffffffu;
-            rays++;
-#ifdef CTL_PROFILE_TRACE
-            const long long pc0 = wall_clock64();
-#endif
-            if (S.n_nodes != 0) {
-                Traverser<2, STATS, SINGLE, WIDE, CTL_ALPHA_OF(FULL)> T;
-                T.anyhit = shadowPhase && shadowAny;
-                T.init(S, v.rori, shadowPhase ? sh.d : v.rdir, 0.0f, S.ray_eps, h.t, st, &ts,
-                       T.anyhit ? sh.dist : -1.0f);
-                while (!T.done) T.round(S, st, &ts);
-                h = T.h;
-                ok &= !st.overflow;
-            }
-#ifdef CTL_PROFILE_TRACE
-            prof_trace += wall_clock64() - pc0;
-#endif
-            // the FULL kernels read parked state where the shading uses it (Park's
-            // partial loads), the lean kernel all of it after the trace
-            constexpr bool lazy = FULL != kShadeLean;
-            if (lazy) park.load_core(v, rng);
-            else park.load(v, sh, rng);
-            bool cont;
-            if (shadowPhase) {
-                if (lazy) { v.cl = park.get3(0); sh.add = park.get3(16); }
-                if (!shadow_occluded(S, shadowAny, h, sh.dist)) v.cl = v.cl + sh.add;
-                shadowPhase = false;
-                cont = !ending && v.depth++ < P.max_path_length;
-                if (lazy && cont) { park.store_cl(v); park.store_depth(v); }
-            } else if (h.tri == 0xffffffffu) {
-                if (lazy) park.load(v, sh, rng);
-                v.cl = v.cl + env_miss<FULL>(S, P, v);   // PathTracer.cu:98-111
-                cont = false;
-            } else {
-                // the FULL kernel keeps the path's first-hit texture partials in its own
-                // sample slot (written only when the path ends), not in four VGPRs
-                // carried through every trace
-                float4* part = PS.s + *pkw;
-                ending = lazy ? !shade_hit<FULL, SINGLE, Park>(S, P, rng, v, h, sh, part, &park)
-                              : !shade_hit<FULL, SINGLE>(S, P, rng, v, h, sh, part);
-                shadowPhase = sh.valid;
-                cont = sh.valid || (!ending && v.depth++ < P.max_path_length);
-                if (lazy && cont) park.store_shaded(v, sh, rng);
-            }
-            if (!cont) {
-                uint32_t px, py, ps, kk;
-                split((uint32_t)*pkw, ps, kk);
-                const PathParams& Pw = FULL ? *opaque_ptr(&P) : P;   // as at the refill
-                work_pixel(Pw, kk, px, py);
-                if (lazy) park.load_px(v);
-                store_sample(Pw, PS, ps, kk, px, py, v.pX, mk3s(1.0f) * v.cl);
-                active = false;
-            } else if (!lazy) {
-                park.store(v, sh, rng);
-            }
-        }
-    }
-    wave_add_u64(&counters[0], rays);
-    if (!ok) atomicAdd(&counters[1], 1ull);
-    if (STATS) {
-        wave_add_u64(&counters[2], ts.nodes);
-        wave_add_u64(&counters[3], ts.tris);
-        wave_add_u64(&counters[4], ts.inst);
-    }
-#ifdef CTL_PROFILE_TRACE
-    // wall-clock ticks (100 MHz) per wave: in the trace call site / in the kernel
-    if (lane == 0) {
-        atomicAdd(&counters[5], (unsigned long long)prof_trace);
-        atomicAdd(&counters[6], (unsigned long long)(wall_clock64() - prof_start));
-    }
-    wave_add_u64(&counters[8], ts.inner_lanes);
-    wave_add_u64(&counters[9], ts.inner_waves);
-    wave_add_u64(&counters[10], ts.leaf_lanes);
-    wave_add_u64(&counters[11], ts.leaf_waves);
-    wave_add_u64(&counters[12], ts.inner_r);
-    wave_add_u64(&counters[13], ts.rounds);
-    wave_add_u64(&counters[14], ts.leafphase_in);
-#endif
+CTL_PERSIST_KERNEL_ATTRS void path_kernel_persistent(DevScene S_arg, PathParams P_arg, const float* s1, const float2* s2,
+                                                     uint64_t items, unsigned long long* cursor,
+                                                     unsigned long long* counters, SampleSlots PS, uint32_t tbl) {
+    using OWN = OwnModulo;
+    const uint32_t* const own_tbl = nullptr;
+#include "persistent_loop.h"
 }
+
+// A block-list pass: one pass per launch (tbl = 0), no traversal statistics.
+template <bool SINGLE, int WIDE, int FULL>
+CTL_PERSIST_KERNEL_ATTRS void path_kernel_persistent_blocks(DevScene S_arg, PathParams P_arg, const float* s1,
+                                                            const float2* s2, uint64_t items, unsigned long long* cursor,
+                                                            unsigned long long* counters, SampleSlots PS,
+                                                            const uint32_t* __restrict__ own_tbl) {
+    using OWN = OwnList;
+    constexpr bool STATS = false;
+    constexpr uint32_t tbl = 0;
+#include "persistent_loop.h"
+}
+#undef CTL_PERSIST_KERNEL_ATTRS
 
 // Batch closest/any hit (intersectKernel<ANY_HIT>, TraceHelper.cu:326-734):
 // ray tmin bounds both the node spans and the triangle test (:650).  Resident
@@ -767,6 +635,10 @@ CTL_API void ctl_destroy(ctl_ctx* c) {
     if (c->d_cursors) (void)hipFree(c->d_cursors);
     if (c->h_overflow) (void)hipHostFree(c->h_overflow);
     if (c->d_tile_flags) (void)hipFree(c->d_tile_flags);
+    if (c->d_block_tbl) (void)hipFree(c->d_block_tbl);
+    if (c->h_block_tbl) (void)hipHostFree(c->h_block_tbl);
+    for (int i = 0; i < 2; i++)
+        if (c->block_ev[i]) (void)hipEventDestroy(c->block_ev[i]);
     for (int i = 0; i < 2; i++)
         if (c->pass_ev[i]) (void)hipEventDestroy(c->pass_ev[i]);
     if (c->d_powers) (void)hipFree(c->d_powers);
@@ -1225,6 +1097,158 @@ CTL_API ctl_status ctl_render_pass(ctl_ctx* c, const ctl_pt_params* params, ctl_
 #else
     return render_pass_speculative(c, params, d_fb, stream);
 #endif
+}
+
+// fold_samples_kernel of a block-list pass: one thread per pixel of a listed
+// block (slot-major, row-major inside the block), so only listed blocks are
+// visited.  The pixel's sources are added in image order, and that m times in
+// succession for a block listed m times -- what m full passes add to it.
+__global__ __launch_bounds__(kBlock) void fold_blocks_kernel(PathParams P, const uint32_t* __restrict__ T,
+                                                             const float4* __restrict__ slots, ctl_pixel* fb) {
+    const uint64_t q = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (q >= P.owned_items) return;
+    const uint32_t ts = P.tile_size, perTile = ts * ts;
+    const uint32_t slot = (uint32_t)(q / perTile), w = (uint32_t)(q % perTile);
+    const uint32_t m = T[OwnList::mult_off(P.num_tiles) + slot];
+    const uint2 o = OwnList::origin(T, slot);
+    const uint32_t x0 = o.x, y0 = o.y;
+    const uint32_t x = x0 + w % ts, y = y0 + w / ts;
+    if (x >= P.width || y >= P.height) return;
+    // sources in image order: (x-1, y-1), (x, y-1), (x-1, y), (x, y); v[i] and
+    // has[i] are indexed by unrolled constants only, so they stay in registers
+    float4 v[4];
+    bool has[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const int d = 3 - i;
+        const uint32_t dx = d & 1, dy = d >> 1;
+        has[i] = false;
+        if (x >= dx && y >= dy) {
+            v[i] = slots[OwnList::source_item(P, T, x - dx, y - dy, slot, x0, y0)];
+            has[i] = v[i].w == (float)(1 + d);
+        }
+    }
+    if (!(has[0] || has[1] || has[2] || has[3])) return;
+    ctl_pixel* pp = fb + (size_t)y * P.width + x;
+    float r = pp->rgb[0], g = pp->rgb[1], b = pp->rgb[2], ws = pp->weight_sum;
+    for (uint32_t k = 0; k < m; k++) {
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            if (has[i]) { r += v[i].x; g += v[i].y; b += v[i].z; ws += 1.0f; }
+        }
+    }
+    pp->rgb[0] = r; pp->rgb[1] = g; pp->rgb[2] = b;
+    pp->weight_sum = ws;
+}
+
+static const char* schedule_name(uint32_t flags) {
+    return (flags & CTL_PT_WAVEFRONT) ? "CTL_PT_WAVEFRONT" : "CTL_PT_MEGAKERNEL";
+}
+
+CTL_API ctl_status ctl_render_pass_blocks(ctl_ctx* c, const ctl_pt_params* p, const uint32_t* blocks, uint32_t n_blocks,
+                                          ctl_pixel* d_fb, void* stream) {
+    if (!c || !p || !d_fb || (!blocks && n_blocks)) return CTL_ERR_INVALID;
+    if (p->flags & (CTL_PT_WAVEFRONT | CTL_PT_MEGAKERNEL)) {
+        c->err = std::string("render_pass_blocks: block lists run in the persistent schedule only, not ") +
+                 schedule_name(p->flags);
+        return CTL_ERR_INVALID;
+    }
+    if (p->num_ranks > 1) { c->err = "render_pass_blocks: num_ranks must be 1"; return CTL_ERR_INVALID; }
+    PathParams P;
+    ctl_status r = prepare_pass(c, p, d_fb, P);
+    if (r != CTL_OK) return r;
+    c->spec.pending = false;   // a render-ahead window does not survive a block-list pass
+    c->spec.last_valid = false;
+    c->spec.streak = 0;
+    if (n_blocks == 0) return CTL_OK;
+    CTL_HIP(c, hipSetDevice(c->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const uint32_t nt = P.num_tiles, ts = P.tile_size;
+    if (c->block_tbl_cap < nt) {
+        for (int i = 0; i < 2; i++) {
+            if (c->block_ev_set[i]) CTL_HIP(c, hipEventSynchronize(c->block_ev[i]));
+            c->block_ev_set[i] = false;
+            if (!c->block_ev[i]) CTL_HIP(c, hipEventCreateWithFlags(&c->block_ev[i], hipEventDisableTiming));
+        }
+        CTL_HIP(c, hipStreamSynchronize(s));
+        if (c->d_block_tbl) (void)hipFree(c->d_block_tbl);
+        if (c->h_block_tbl) (void)hipHostFree(c->h_block_tbl);
+        c->d_block_tbl = nullptr; c->h_block_tbl = nullptr; c->block_tbl_cap = 0;
+        if (hipMalloc(&c->d_block_tbl, OwnList::words(nt) * sizeof(uint32_t)) != hipSuccess ||
+            hipHostMalloc(&c->h_block_tbl, 2 * OwnList::words(nt) * sizeof(uint32_t)) != hipSuccess) {
+            c->err = "render_pass_blocks: block table allocation failed";
+            return CTL_ERR_NOMEM;
+        }
+        c->block_tbl_cap = nt;
+    }
+    // the staging half of two calls ago: its upload has usually long left it
+    const uint32_t half = c->block_half;
+    if (c->block_ev_set[half]) CTL_HIP(c, hipEventSynchronize(c->block_ev[half]));
+    // OwnList tables (common.h): slots in order of first appearance in the list
+    uint32_t* origin = c->h_block_tbl + half * OwnList::words(c->block_tbl_cap);
+    uint32_t* slot_of = origin + OwnList::slot_of_off(nt);
+    uint32_t* mult = origin + OwnList::mult_off(nt);
+    std::fill(origin, origin + 2 * (size_t)nt, 0u);
+    std::fill(slot_of, slot_of + nt, kUnlisted);
+    std::fill(mult, mult + nt, 0u);
+    uint32_t n_slots = 0;
+    for (uint32_t i = 0; i < n_blocks; i++) {
+        const uint32_t b = blocks[i];
+        if (b >= nt) {
+            c->err = "render_pass_blocks: block id " + std::to_string(b) + " >= " + std::to_string(nt) + " blocks";
+            return CTL_ERR_INVALID;
+        }
+        if (slot_of[b] == kUnlisted) {
+            origin[2 * n_slots] = (b % P.tiles_x) * ts;
+            origin[2 * n_slots + 1] = (b / P.tiles_x) * ts;
+            slot_of[b] = n_slots++;
+        }
+        if (++mult[slot_of[b]] > 255) {
+            c->err = "render_pass_blocks: block " + std::to_string(b) + " listed more than 255 times";
+            return CTL_ERR_INVALID;
+        }
+    }
+    P.apron = 2 * ts + 1;
+    const uint64_t own = (uint64_t)n_slots * ts * ts, items = own + (uint64_t)n_slots * P.apron;
+    if (items > kListItemMask) { c->err = "render_pass_blocks: 2^29 or more work items"; return CTL_ERR_INVALID; }
+    P.owned_items = (uint32_t)own;
+    CTL_HIP(c, hipEventRecord(c->pass_ev[0], s));
+    CTL_HIP(c, hipMemcpyAsync(c->d_block_tbl, origin, OwnList::words(nt) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    CTL_HIP(c, hipEventRecord(c->block_ev[half], s));
+    c->block_ev_set[half] = true;
+    c->block_half = half ^ 1;
+    r = prepare_slots(c, items, s);
+    if (r != CTL_OK) return r;
+    unsigned long long* cursor = c->d_cursors + 1;
+    CTL_HIP(c, hipMemsetAsync(cursor, 0, sizeof(unsigned long long), s));
+    const bool single = c->scene.single != 0, wide = c->scene.wide != 0;
+    const uint32_t full = c->scene.full_shading;
+    const uint64_t want = (items + kBlock - 1) / kBlock;
+    const SampleSlots PS = make_slots(c->d_slices, (uint32_t)items);
+    const float* s1 = c->d_s1[c->active];
+    const float2* s2 = c->d_s2[c->active];
+#define PKL(SG, WD, FU)                                                                                          \
+    do {                                                                                                         \
+        constexpr size_t lds = persistent_lds_bytes();                                                          \
+        int nb = resident_blocks(c, path_kernel_persistent_blocks<SG, WD, FU>, lds);                             \
+        if (CTL_PERSIST_BPC > 0) nb = std::min(nb, CTL_PERSIST_BPC * c->cu_count);                              \
+        hipLaunchKernelGGL((path_kernel_persistent_blocks<SG, WD, FU>),                                          \
+                           dim3((unsigned)std::min<uint64_t>(nb, want)), dim3(kBlock), lds, s, c->scene, P, s1,  \
+                           s2, items, cursor, c->d_counters, PS, (const uint32_t*)c->d_block_tbl);               \
+    } while (0)
+#define PKL2(SG, WD) do { if (full == kShadeEnv) PKL(SG, WD, kShadeEnv); else if (full == kShadeAlpha) PKL(SG, WD, kShadeAlpha); \
+                          else if (full) PKL(SG, WD, kShadeFull); else PKL(SG, WD, kShadeLean); } while (0)
+    if (wide) { if (single) PKL2(true, 1); else PKL2(false, 1); }
+    else { if (single) PKL2(true, 0); else PKL2(false, 0); }
+#undef PKL2
+#undef PKL
+    CTL_HIP(c, hipGetLastError());
+    hipLaunchKernelGGL(fold_blocks_kernel, dim3((unsigned)((own + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, P,
+                       (const uint32_t*)c->d_block_tbl, (const float4*)c->d_slices, d_fb);
+    CTL_HIP(c, hipGetLastError());
+    CTL_HIP(c, hipEventRecord(c->pass_ev[1], s));
+    c->pass_timed = true;
+    return CTL_OK;
 }
 
 CTL_API ctl_status ctl_last_pass_ms(ctl_ctx* c, float* ms) {

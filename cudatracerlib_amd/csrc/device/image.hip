@@ -4,6 +4,7 @@
 //   variance_add_kernel    PixelVarianceInfo::updateMoments        Kernel/PixelVarianceBuffer.h:22-41
 //                          (launched like updateVarianceBuffer,    Kernel/PixelVarianceBuffer.cu:10-37)
 //   variance_stats_kernel  computeError / computeVariance / computeAverage, PixelVarianceBuffer.h:43-62
+//   block_stats_kernel     updateInfo (per-block sums for the block sampler), BlockSampler/VarianceBlockSampler.cu:7-30
 // One thread per pixel, 256-thread blocks; everything is HBM-streaming work
 // (28 B in, 4 B out per pixel for the resolve).  fp32, reference op order.
 #include <hip/hip_runtime.h>
@@ -90,6 +91,61 @@ __global__ __launch_bounds__(kBlock) void variance_stats_kernel(const ctl_pixel_
     if (average) average[i] = v.sum_x / N;
 }
 
+// updateInfo (VarianceBlockSampler.cu:7-30) without its float atomics: one
+// workgroup per block.  Lane t sums the block's pixels t, t + 256, ... (row-major
+// inside the block's rectangle in the image) in that order, the 64 lanes of a
+// wave are combined by a butterfly (every lane ends with the same bits), and
+// lane 0 adds the four wave sums from LDS in wave order.  So the result depends
+// on the image and the block size only, never on arrival order.
+__global__ __launch_bounds__(kBlock) void block_stats_kernel(const ctl_pixel_variance* var, uint32_t w, uint32_t h,
+                                                             uint32_t tile, uint32_t tiles_x, ctl_block_info* out) {
+    const uint32_t bidx = blockIdx.x;
+    const uint32_t x0 = (bidx % tiles_x) * tile, y0 = (bidx / tiles_x) * tile;
+    const uint32_t bw = w - x0 < tile ? w - x0 : tile, bh = h - y0 < tile ? h - y0 : tile;
+    const uint64_t n = (uint64_t)bw * bh;
+    float sv = 0.0f, se = 0.0f, se2 = 0.0f;
+    uint32_t nv = 0, ne = 0;
+    for (uint64_t i = threadIdx.x; i < n; i += kBlock) {
+        const uint32_t x = x0 + (uint32_t)(i % bw), y = y0 + (uint32_t)(i / bw);
+        const ctl_pixel_variance v = var[(size_t)y * w + x];
+        // computeVariance / computeAverage as variance_stats_kernel
+        const float N = (float)v.num_samples_var;
+        const float invN = 1.0f / N;
+        const float variance = (v.sum_x2 - (v.sum_x * v.sum_x) * invN) * invN;
+        const float e = v.sum_x / N;
+        if (variance >= 0 && !isnan(variance)) { sv += variance; nv++; }
+        se += e;
+        se2 += e * e;
+        ne++;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        sv += __shfl_xor(sv, off);
+        se += __shfl_xor(se, off);
+        se2 += __shfl_xor(se2, off);
+        nv += (uint32_t)__shfl_xor((int)nv, off);
+        ne += (uint32_t)__shfl_xor((int)ne, off);
+    }
+    __shared__ float red_f[3][kBlock / 64];
+    __shared__ uint32_t red_u[2][kBlock / 64];
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        red_f[0][wave] = sv; red_f[1][wave] = se; red_f[2][wave] = se2;
+        red_u[0][wave] = nv; red_u[1][wave] = ne;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        ctl_block_info b;
+        b.block_var_i = ((red_f[0][0] + red_f[0][1]) + red_f[0][2]) + red_f[0][3];
+        b.block_e_i = ((red_f[1][0] + red_f[1][1]) + red_f[1][2]) + red_f[1][3];
+        b.block_e_i2 = ((red_f[2][0] + red_f[2][1]) + red_f[2][2]) + red_f[2][3];
+        b.num_pixels_var = red_u[0][0] + red_u[0][1] + red_u[0][2] + red_u[0][3];
+        b.num_pixels_e = red_u[1][0] + red_u[1][1] + red_u[1][2] + red_u[1][3];
+        out[bidx] = b;
+    }
+}
+static_assert(kBlock == 256, "block_stats_kernel adds four wave sums");
+
 }  // namespace
 }  // namespace ctl
 
@@ -154,6 +210,21 @@ CTL_API ctl_status ctl_variance_stats(ctl_ctx* c, const ctl_pixel_variance* var,
     CTL_HIP(c, hipSetDevice(c->device));
     hipLaunchKernelGGL(variance_stats_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0,
                        reinterpret_cast<hipStream_t>(stream), var, n, err, variance, average);
+    CTL_HIP(c, hipGetLastError());
+    return CTL_OK;
+}
+
+CTL_API ctl_status ctl_block_stats(ctl_ctx* c, const ctl_pixel_variance* var, uint32_t w, uint32_t h, uint32_t tile,
+                                   ctl_block_info* out, void* stream) {
+    if (!c || !tile || ((!var || !out) && (uint64_t)w * h)) return CTL_ERR_INVALID;
+    const uint64_t n = (uint64_t)w * h;
+    if (n == 0) return CTL_OK;
+    if (n > 0xffffffffull) { c->err = "block_stats: image too large"; return CTL_ERR_INVALID; }
+    const uint64_t tx = ((uint64_t)w + tile - 1) / tile, ty = ((uint64_t)h + tile - 1) / tile;
+    if (tx * ty > 0x7fffffffull) { c->err = "block_stats: too many blocks for one launch"; return CTL_ERR_INVALID; }
+    CTL_HIP(c, hipSetDevice(c->device));
+    hipLaunchKernelGGL(block_stats_kernel, dim3((unsigned)(tx * ty)), dim3(kBlock), 0,
+                       reinterpret_cast<hipStream_t>(stream), var, w, h, tile, (uint32_t)tx, out);
     CTL_HIP(c, hipGetLastError());
     return CTL_OK;
 }

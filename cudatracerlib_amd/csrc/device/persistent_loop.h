@@ -1,0 +1,176 @@
+// The loop of the persistent path kernels, included as the body of both kernel
+// templates in ctl_trace.hip (path_kernel_persistent, path_kernel_persistent_blocks)
+// so that each compiles exactly as if it were written out.  The including kernel
+// provides: template parameters STATS, SINGLE, WIDE, FULL; the type OWN (ownership
+// policy, common.h); its arguments S_arg, P_arg, s1, s2, items, cursor, counters,
+// PS, tbl; and own_tbl (OwnList's tables, never read under OwnModulo).
+    // Work item k renders pass slot k / PS.per_pass (sampler tables at
+    // s1/s2 + slot * tbl) of work item k % PS.per_pass; every finished sample
+    // goes to its own slot, folded into the framebuffer afterwards (store_sample).
+    // The scene and pass records are read in place from the kernel-argument
+    // segment (scalar loads at their uses) rather than held in SGPRs for the
+    // kernel's lifetime: 100+ live SGPRs spilled into VGPR lanes and from
+    // there to scratch.  C3 3184 -> 3310, C5 1662 -> 1772 Mrays/s; VGPR spills
+    // lean 10 -> 0, full 98 -> 40 (profiles/r03_park_slack_ab.txt).
+    const DevScene& S = kernarg_ref<DevScene>(S_arg, 0);
+    const PathParams& P = kernarg_ref<PathParams>(P_arg, kernarg_next<DevScene, PathParams>(0));
+    // OwnList: the item -> pixel map goes through tables, so it is evaluated once, at
+    // the refill: the sample's landing code (all store_sample needs of the pixel) rides
+    // in the top bits of the parked work item word (items < 2^kListItemBits, host).
+    constexpr bool kList = std::is_same<OWN, OwnList>::value;
+    CTL_LANE_STACK(st);
+    SamplerDev rng{s1, s2, P.nseq, P.len, 0, 0, 0, 0};
+    // work item of the lane's path (pass slot * PS.per_pass + item), parked in
+    // LDS for the path's lifetime instead of holding a VGPR through the traces
+    int* pkw = ctl_lds_stack + kPathWordOff + threadIdx.x;
+    const Park park{(int)threadIdx.x};
+    auto split = [&](uint32_t k, uint32_t& ps, uint32_t& kk) { PS.split(k, ps, kk); };
+    PathVars v;
+    ShadowReq sh;
+    sh.valid = false;
+    sh.dist = 0.0f;
+    TraceStats ts{0, 0, 0};
+    uint32_t rays = 0;
+    bool active = false, exhausted = false, shadowPhase = false, ending = false, ok = true;
+#ifdef CTL_PROFILE_TRACE
+    long long prof_trace = 0;
+    const long long prof_start = wall_clock64();
+#endif
+    const bool shadowAny = P.shadow_any_hit != 0;
+    const int lane = threadIdx.x & 63;
+    while (true) {
+        const bool need = !active && !exhausted;
+        const uint64_t mask = __ballot(need);
+        if (mask) {
+            const int leader = __ffsll((unsigned long long)mask) - 1;
+            unsigned long long base = 0;
+            if (lane == leader) base = atomicAdd(cursor, (unsigned long long)__popcll(mask));
+            base = __shfl(base, leader);
+            if (need) {
+                const uint64_t k64 = base + (uint64_t)lanes_below(mask);
+                if (k64 >= items) {
+                    exhausted = true;
+                } else {
+                    const uint32_t k = (uint32_t)k64;   // items < 2^32 (checked on the host)
+                    uint32_t px, py, ps, kk;
+                    split(k, ps, kk);
+                    // FULL: the pass record read through an opaque pointer here, so the
+                    // divisions by its fields keep their reciprocals local to the refill
+                    // (hoisted, they held VGPRs the FULL kernel spilled for its lifetime;
+                    // the lean kernel has the registers and keeps them hoisted)
+                    const PathParams& Pw = FULL ? *opaque_ptr(&P) : P;
+                    const uint32_t* const T = own_tbl;
+                    if (OWN::work_pixel(Pw, T, kk, px, py)) {
+                        const uint32_t idx = py * Pw.width + px;
+                        // the pass slot's tables start ps * tbl elements in: folded into
+                        // the two sequence offsets so the table bases stay kernel-uniform
+                        rng.a = idx % Pw.nseq + ps * tbl; rng.b = (idx / Pw.nseq) % Pw.nseq + ps * tbl;
+                        rng.d1 = 0; rng.d2 = 0;
+                        if constexpr (!kList) *pkw = (int)k;
+                        f3 o, dw;
+                        const f2 pX = primary_ray(S, rng, px, py, o, dw);
+                        if constexpr (kList) *pkw = (int)(k | landing_code(Pw, px, py, pX) << kListItemBits);
+                        v.begin(pX, o, dw);
+                        shadowPhase = false;
+                        ending = false;
+                        // loop head of PathTrace: `while (depth++ < MaxPathLength)`
+                        if (!OWN::apron_keep(Pw, T, kk, pX)) PS.s[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                        else if (v.depth++ < P.max_path_length) active = true;
+                        else store_sample(P, PS, ps, kk, px, py, v.pX, mk3s(1.0f) * v.cl);
+                        if (active) park.begin(v, rng);
+                    } else {
+                        PS.s[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);   // work item outside the image: no sample
+                    }
+                }
+            }
+        }
+        if (!__any(active)) {
+            if (__all(exhausted)) break;
+            continue;
+        }
+        if (active) {
+            HitRec h;
+            h.t = (shadowPhase && shadowAny) ? sh.dist - S.ray_eps : FLT_MAX;
+            h.u = h.v = 0.0f; h.tri = 0xffffffffu; h.node = 0xffffffffu;
+            rays++;
+#ifdef CTL_PROFILE_TRACE
+            const long long pc0 = wall_clock64();
+#endif
+            if (S.n_nodes != 0) {
+                Traverser<2, STATS, SINGLE, WIDE, CTL_ALPHA_OF(FULL)> T;
+                T.anyhit = shadowPhase && shadowAny;
+                T.init(S, v.rori, shadowPhase ? sh.d : v.rdir, 0.0f, S.ray_eps, h.t, st, &ts,
+                       T.anyhit ? sh.dist : -1.0f);
+                while (!T.done) T.round(S, st, &ts);
+                h = T.h;
+                ok &= !st.overflow;
+            }
+#ifdef CTL_PROFILE_TRACE
+            prof_trace += wall_clock64() - pc0;
+#endif
+            // the FULL kernels read parked state where the shading uses it (Park's
+            // partial loads), the lean kernel all of it after the trace
+            constexpr bool lazy = FULL != kShadeLean;
+            if (lazy) park.load_core(v, rng);
+            else park.load(v, sh, rng);
+            bool cont;
+            if (shadowPhase) {
+                if (lazy) { v.cl = park.get3(0); sh.add = park.get3(16); }
+                if (!shadow_occluded(S, shadowAny, h, sh.dist)) v.cl = v.cl + sh.add;
+                shadowPhase = false;
+                cont = !ending && v.depth++ < P.max_path_length;
+                if (lazy && cont) { park.store_cl(v); park.store_depth(v); }
+            } else if (h.tri == 0xffffffffu) {
+                if (lazy) park.load(v, sh, rng);
+                v.cl = v.cl + env_miss<FULL>(S, P, v);   // PathTracer.cu:98-111
+                cont = false;
+            } else {
+                // the FULL kernel keeps the path's first-hit texture partials in its own
+                // sample slot (written only when the path ends), not in four VGPRs
+                // carried through every trace
+                float4* part = kList ? PS.s + ((uint32_t)*pkw & kListItemMask) : PS.s + *pkw;
+                ending = lazy ? !shade_hit<FULL, SINGLE, Park>(S, P, rng, v, h, sh, part, &park)
+                              : !shade_hit<FULL, SINGLE>(S, P, rng, v, h, sh, part);
+                shadowPhase = sh.valid;
+                cont = sh.valid || (!ending && v.depth++ < P.max_path_length);
+                if (lazy && cont) park.store_shaded(v, sh, rng);
+            }
+            if (!cont) {
+                if constexpr (kList) {
+                    const uint32_t wd = (uint32_t)*pkw;   // one pass per launch: the item is the slot
+                    store_sample_coded(PS, wd & kListItemMask, wd >> kListItemBits, mk3s(1.0f) * v.cl);
+                } else {
+                    uint32_t px, py, ps, kk;
+                    split((uint32_t)*pkw, ps, kk);
+                    const PathParams& Pw = FULL ? *opaque_ptr(&P) : P;   // as at the refill
+                    OWN::work_pixel(Pw, own_tbl, kk, px, py);
+                    if (lazy) park.load_px(v);
+                    store_sample(Pw, PS, ps, kk, px, py, v.pX, mk3s(1.0f) * v.cl);
+                }
+                active = false;
+            } else if (!lazy) {
+                park.store(v, sh, rng);
+            }
+        }
+    }
+    wave_add_u64(&counters[0], rays);
+    if (!ok) atomicAdd(&counters[1], 1ull);
+    if (STATS) {
+        wave_add_u64(&counters[2], ts.nodes);
+        wave_add_u64(&counters[3], ts.tris);
+        wave_add_u64(&counters[4], ts.inst);
+    }
+#ifdef CTL_PROFILE_TRACE
+    // wall-clock ticks (100 MHz) per wave: in the trace call site / in the kernel
+    if (lane == 0) {
+        atomicAdd(&counters[5], (unsigned long long)prof_trace);
+        atomicAdd(&counters[6], (unsigned long long)(wall_clock64() - prof_start));
+    }
+    wave_add_u64(&counters[8], ts.inner_lanes);
+    wave_add_u64(&counters[9], ts.inner_waves);
+    wave_add_u64(&counters[10], ts.leaf_lanes);
+    wave_add_u64(&counters[11], ts.leaf_waves);
+    wave_add_u64(&counters[12], ts.inner_r);
+    wave_add_u64(&counters[13], ts.rounds);
+    wave_add_u64(&counters[14], ts.leafphase_in);
+#endif

@@ -494,6 +494,35 @@ CTL_API ctl_status ctl_render_pass(ctl_ctx* ctx, const ctl_pt_params* params, ct
 CTL_API ctl_status ctl_render_passes(ctl_ctx* ctx, const ctl_pt_params* params, uint64_t first_pass,
                                      uint32_t n_passes, ctl_pixel* d_fb, void* stream);
 
+/* One pass over a list of blocks (Tracer<true>::DoRender over the blocks an
+ * IBlockSampler yields, Kernel/Tracer.h:264-289): a full pass masked to the
+ * listed blocks.  `blocks` is a host array of n_blocks row-major block ids
+ * (IBlockSampler::getFlattenedIdx) over ceil(w/ts) x ceil(h/ts), ts =
+ * params->tile_size (0 = 64); the caller may reuse it on return.  An id may
+ * repeat: its multiplicity m (1..255) is the block-flag value of
+ * ctl_variance_add_pass.  Every pixel of a listed block receives what
+ * ctl_render_pass would add to it with the current sampler tables, m times in
+ * succession; pixels of unlisted blocks are not written.  The sampler has no
+ * per-pixel state, so a repeated block gets the identical sample again: it is
+ * traced once and added m times, and ctl_rays_traced counts the paths actually
+ * traced.  A sample whose jitter carries it into a neighbouring block is
+ * summed by the block it lands on, traced there when its own block is not
+ * listed, and dropped when it leaves the list, so disjoint
+ * lists rendered one after the other give the full pass bit for bit.
+ * num_ranks must be 1 and the schedule the persistent one (CTL_PT_MEGAKERNEL /
+ * CTL_PT_WAVEFRONT: CTL_ERR_INVALID); CTL_PT_RENDER_AHEAD is ignored and a
+ * pending window is dropped.  A block id past the block count or a
+ * multiplicity over 255 is CTL_ERR_INVALID, as is a list of 2^29 or more work
+ * items (pixels of the listed blocks); n_blocks == 0 writes nothing.
+ * Asynchronous on `stream`, up to two calls deep: the block tables go up from
+ * two staging buffers used in turn, so a call first waits on the host until
+ * the table upload of the call before last has executed (a caller queueing
+ * list passes without synchronising runs about two passes ahead of the
+ * device), and a call for an image of more blocks than any before
+ * synchronises `stream` once to grow the tables.  ctl_last_pass_ms covers the call. */
+CTL_API ctl_status ctl_render_pass_blocks(ctl_ctx* ctx, const ctl_pt_params* params, const uint32_t* blocks,
+                                          uint32_t n_blocks, ctl_pixel* d_fb, void* stream);
+
 /* Device time of the last ctl_render_pass on its stream, in milliseconds
  * (Tracer::getLastTimeSpentRenderingSec, Kernel/Tracer.h:133-140, which times
  * DoPass with cudaEvents, Tracer.h:213,239-244).  Waits for that pass. */
@@ -729,6 +758,66 @@ CTL_API ctl_status ctl_variance_add_pass(ctl_ctx* ctx, const ctl_pixel* d_fb, ui
  * (PixelVarianceBuffer.h:43-62) for n records; any output may be NULL. */
 CTL_API ctl_status ctl_variance_stats(ctl_ctx* ctx, const ctl_pixel_variance* d_var, uint64_t n, float* d_error,
                                       float* d_variance, float* d_average, void* stream);
+
+/* ---- adaptive sampling (Kernel/BlockSampler) ------------------------------ */
+
+/* VarianceBlockSampler::TmpBlockInfo (VarianceBlockSampler.h:15-23), 20 B. */
+typedef struct {
+    float block_var_i;        /* sum of the pixel variances that are >= 0      */
+    uint32_t num_pixels_var;  /* ... and how many joined it                    */
+    float block_e_i;          /* sum of the pixel averages e                   */
+    float block_e_i2;         /* sum of e * e                                  */
+    uint32_t num_pixels_e;    /* pixels of the block inside the image          */
+} ctl_block_info;
+
+/* updateInfo (VarianceBlockSampler.cu:7-30): the per-block sums of
+ * computeVariance / computeAverage (as ctl_variance_stats computes them) into
+ * d_out[ceil(w/tile_size) * ceil(h/tile_size)], row-major.  A variance joins
+ * block_var_i only when it is >= 0 and not NaN; e and e * e always join, so a
+ * pixel without a variance sample makes block_e_i NaN, as in the reference.
+ * One workgroup per block summing in a fixed order, no float atomics: the
+ * result is bitwise reproducible (the reference's depends on arrival order).
+ * Asynchronous. */
+CTL_API ctl_status ctl_block_stats(ctl_ctx* ctx, const ctl_pixel_variance* d_var, uint32_t width, uint32_t height,
+                                   uint32_t tile_size, ctl_block_info* d_out, void* stream);
+
+/* IBlockSampler (host only, no GPU): which blocks the next pass renders.
+ * UNIFORM: every block once.  VARIANCE (VarianceBlockSampler): every block
+ * once until 10 passes are done, then the first N / frac_weighted blocks by
+ * descending weight followed by the blocks passes_done % frac_deterministic,
+ * + frac_deterministic, ... (MixedBlockIterate, IBlockSampler.h:131-154).
+ * weight = (0.85 w1n + 0.15 w2n) * userWeight^2, w1 = sqrt(block_var_i /
+ * num_pixels_var) (0 without pixels), w2 = sqrt(block_e_i2 / n - (block_e_i /
+ * n)^2), both min/max-normalised over all blocks.  Fixed where the reference
+ * leaves it open: a NaN weight ranks below every number, equal weights rank by
+ * ascending block id, each pass sorts afresh.  The per-block pass counts are
+ * of what was rendered (the reference counts the next pass's list). */
+typedef struct ctl_block_sampler ctl_block_sampler;
+enum { CTL_BST_UNIFORM = 0, CTL_BST_VARIANCE = 1 };
+/* NULL on bad arguments (ctl_host_last_error, as for every call below) */
+CTL_API ctl_block_sampler* ctl_block_sampler_create(uint32_t width, uint32_t height, uint32_t tile_size,
+                                                    uint32_t type);
+CTL_API void ctl_block_sampler_destroy(ctl_block_sampler* s);
+/* passes done, ranking, weights and per-block counts reset; user weights and fractions kept */
+CTL_API ctl_status ctl_block_sampler_start_new_rendering(ctl_block_sampler* s);
+/* KEY_FractionDeterministic (2) / KEY_FractionWeighted (4), both >= 1 */
+CTL_API ctl_status ctl_block_sampler_set_fractions(ctl_block_sampler* s, uint32_t frac_deterministic,
+                                                   uint32_t frac_weighted);
+/* IUserPreferenceSampler::setWeight (default 1) */
+CTL_API ctl_status ctl_block_sampler_set_user_weight(ctl_block_sampler* s, uint32_t bx, uint32_t by, float w);
+/* IterateBlocks: the next pass's list for ctl_render_pass_blocks.  *n = its
+ * length; with capacity < *n nothing is written and CTL_ERR_INVALID returned. */
+CTL_API ctl_status ctl_block_sampler_blocks(const ctl_block_sampler* s, uint32_t* out, uint32_t capacity,
+                                            uint32_t* n);
+/* the same list as one count per block (ctl_variance_add_pass's tile_samples) */
+CTL_API ctl_status ctl_block_sampler_tile_samples(const ctl_block_sampler* s, uint8_t* out);
+/* AddPass: the finished pass's ctl_block_stats, read back (n = block count;
+ * ignored by the UNIFORM sampler, where info may be NULL) */
+CTL_API ctl_status ctl_block_sampler_add_pass(ctl_block_sampler* s, const ctl_block_info* info, uint32_t n);
+/* the weights of the last add_pass, one per block (what visualizeWeights draws) */
+CTL_API ctl_status ctl_block_sampler_weights(const ctl_block_sampler* s, float* out);
+/* IBlockSampler::BlockInfo::passesDone, one per block */
+CTL_API ctl_status ctl_block_sampler_passes_done(const ctl_block_sampler* s, uint32_t* out);
 
 /* Number of traceRay-equivalent queries (camera + bounce + shadow rays +
  * batched rays) since the last reset; 64-bit (the reference's counter is a
