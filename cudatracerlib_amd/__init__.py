@@ -27,13 +27,17 @@ import os
 import numpy as np
 
 from . import _abi
+from ._abi import (ImageFilter, Tonemap, LuminanceInfo, CTL_FILTER_BOX, CTL_FILTER_GAUSSIAN, CTL_FILTER_MITCHELL,
+                   CTL_FILTER_LANCZOS, CTL_FILTER_TRIANGLE, CTL_FILTER_NLM, CTL_NLM_DIRECT)
 from ._abi import (PTParams, WptParams, PrimParams, SceneDesc, Material, Pixel, Ray, Hit, CTL_SCENE_HALF_HOST_QUIRK, CTL_SCENE_BINARY_BVH,
                    CTL_BSDF_DIFFUSE, CTL_EDIFFUSE_REFLECTION, CTL_PT_MEGAKERNEL, CTL_PT_WAVEFRONT, CTL_PT_RENDER_AHEAD,
                    CTL_COMM_ID_BYTES)
 
 __all__ = ["HostScene", "Tracer", "PathTracer", "BlockSampler", "BLOCK_INFO_DTYPE", "WavefrontPathTracer", "PrimTracer", "PrimParams", "WptParams", "PTParams", "SceneDesc", "Material", "Pixel", "Ray", "Hit",
            "roughdielectric_material", "set_alpha_map", "comm_unique_id", "comm_init_rank", "comm_init_all",
-           "comm_destroy",
+           "comm_destroy", "ImageFilter", "Tonemap", "LuminanceInfo", "image_filter", "filter_evaluate", "rgbe_encode",
+           "rgbe_decode", "tonemap_constants", "CTL_FILTER_BOX", "CTL_FILTER_GAUSSIAN", "CTL_FILTER_MITCHELL",
+           "CTL_FILTER_LANCZOS", "CTL_FILTER_TRIANGLE", "CTL_FILTER_NLM", "CTL_NLM_DIRECT",
            "CTL_SCENE_HALF_HOST_QUIRK", "CTL_SCENE_BINARY_BVH", "CTL_PT_MEGAKERNEL", "CTL_PT_WAVEFRONT", "CTL_PT_RENDER_AHEAD", "lib", "diffuse_material"]
 
 
@@ -95,6 +99,52 @@ def roughdielectric_material(distribution, eta, alpha_u, alpha_v=None, reflectan
     m.alpha_v = float(alpha_u if alpha_v is None else alpha_v)
     m.sample_visible = 1                                         # getSampleVisible(Beckmann/GGX, true)
     return m
+
+
+# the reference's default parameters per filter type: (x_width, y_width, a, b)
+_FILTER_DEFAULTS = {CTL_FILTER_BOX: (1.0, 1.0, 0.0, 0.0), CTL_FILTER_GAUSSIAN: (2.0, 2.0, -2.0, 0.0),
+                    CTL_FILTER_MITCHELL: (2.0, 2.0, 1.0 / 3.0, 1.0 / 3.0), CTL_FILTER_LANCZOS: (6.0, 6.0, 3.0, 0.0),
+                    CTL_FILTER_TRIANGLE: (2.0, 2.0, 0.0, 0.0), CTL_FILTER_NLM: (0.0, 0.0, 0.0, 0.0)}
+
+
+def image_filter(type, x_width=None, y_width=None, a=None, b=None, k=0.45, sigma2_scale=0.005, update_periodicity=25,
+                 flags=0):
+    """An ImageFilter (ctl_image_filter) of `type` with the reference's defaults (SceneTypes/Filter.h
+    constructors, NonLocalMeansFilter's settings) for every parameter left None."""
+    d = _FILTER_DEFAULTS.get(int(type), (0.0, 0.0, 0.0, 0.0))
+    v = [d[i] if x is None else float(x) for i, x in enumerate((x_width, y_width, a, b))]
+    return ImageFilter(int(type), v[0], v[1], v[2], v[3], float(k), float(sigma2_scale), int(update_periodicity),
+                       int(flags))
+
+
+def filter_evaluate(filter, x, y):
+    """Filter::Evaluate(x, y) of a canonical filter as the kernels compute it (ctl_filter_evaluate, host)."""
+    out = C.c_float()
+    _check(lib().ctl_filter_evaluate(C.byref(filter), float(x), float(y), C.byref(out)), None, "ctl_filter_evaluate")
+    return np.float32(out.value)
+
+
+def rgbe_encode(rgb):
+    """Spectrum::toRGBE of linear (r, g, b): one uint32, r in the low byte (ctl_rgbe_encode, host)."""
+    v = (C.c_float * 3)(*np.asarray(rgb, dtype=np.float32).reshape(3).tolist())
+    out = C.c_uint32()
+    _check(lib().ctl_rgbe_encode(v, C.byref(out)), None, "ctl_rgbe_encode")
+    return int(out.value)
+
+
+def rgbe_decode(word):
+    """Spectrum::fromRGBE as float32[3] (ctl_rgbe_decode, host)."""
+    v = (C.c_float * 3)()
+    _check(lib().ctl_rgbe_decode(int(word) & 0xFFFFFFFF, v), None, "ctl_rgbe_decode")
+    return np.array(list(v), dtype=np.float32)
+
+
+def tonemap_constants(tonemap, avg_log_lum, max_lum):
+    """ToneMapPostProcess::Apply's (scale, 1 / Lwhite^2 burn^4) (ctl_tonemap_constants, host)."""
+    s, i = C.c_float(), C.c_float()
+    _check(lib().ctl_tonemap_constants(C.byref(tonemap), float(avg_log_lum), float(max_lum), C.byref(s), C.byref(i)),
+           None, "ctl_tonemap_constants")
+    return np.float32(s.value), np.float32(i.value)
 
 
 class HostScene:
@@ -564,6 +614,25 @@ class Tracer:
         """applyImagePipeline without filter/post-process: RGBA8 sRGB output (ImagePipeline.cu)."""
         _check(self._L.ctl_image_resolve(self._ctx, fb_ptr, width, height, float(splat_scale), out_ptr, stream),
                self._ctx, "ctl_image_resolve")
+
+    def image_pipeline(self, fb_ptr, width, height, out_ptr, filter=None, tonemap=None, var_ptr=None,
+                       filtered_ptr=None, splat_scale=0.0, num_passes=0, stream=0):
+        """applyImagePipeline (ctl_image_pipeline): `filter` an ImageFilter (image_filter(...)) or None,
+        `tonemap` a Tonemap or None; RGBA8 into out_ptr, the filtered RGBE image into filtered_ptr when
+        given.  CTL_FILTER_NLM needs var_ptr (PixelVariance records) and keeps its weights in the
+        context between calls with consecutive num_passes (update_periodicity)."""
+        _check(self._L.ctl_image_pipeline(self._ctx, fb_ptr, var_ptr, int(width), int(height), float(splat_scale),
+                                          int(num_passes), C.byref(filter) if filter is not None else None,
+                                          C.byref(tonemap) if tonemap is not None else None, filtered_ptr, out_ptr,
+                                          stream), self._ctx, "ctl_image_pipeline")
+
+    def image_luminance(self, rgbe_ptr, width, height, stream=0):
+        """Image::ComputeLuminanceInfo of a device RGBE image (ctl_image_luminance) as a LuminanceInfo;
+        fixed summation order, so bitwise reproducible.  Synchronises."""
+        out = LuminanceInfo()
+        _check(self._L.ctl_image_luminance(self._ctx, rgbe_ptr, int(width), int(height), C.byref(out), stream),
+               self._ctx, "ctl_image_luminance")
+        return out
 
     def variance_add_pass(self, fb_ptr, width, height, tile_samples, var_ptr, splat_scale=0.0, tile_size=64,
                           stream=0):

@@ -183,6 +183,26 @@ class BlockInfo(C.Structure):        # VarianceBlockSampler::TmpBlockInfo, 20 B
 
 CTL_BST_UNIFORM, CTL_BST_VARIANCE = 0, 1   # ctl_block_sampler_create types
 
+# ctl_image_filter.type (Filter.h TYPE_FUNC ids, NonLocalMeansFilter) and .flags
+CTL_FILTER_BOX, CTL_FILTER_GAUSSIAN, CTL_FILTER_MITCHELL, CTL_FILTER_LANCZOS, CTL_FILTER_TRIANGLE = 1, 2, 3, 4, 5
+CTL_FILTER_NLM = 16
+CTL_NLM_DIRECT = 1 << 0
+
+
+class ImageFilter(C.Structure):      # ctl_image_filter, 36 B
+    _fields_ = [("type", C.c_uint32), ("x_width", C.c_float), ("y_width", C.c_float), ("a", C.c_float),
+                ("b", C.c_float), ("k", C.c_float), ("sigma2_scale", C.c_float), ("update_periodicity", C.c_uint32),
+                ("flags", C.c_uint32)]
+
+
+class Tonemap(C.Structure):          # ctl_tonemap (ToneMapPostProcess), 8 B
+    _fields_ = [("key", C.c_float), ("burn", C.c_float)]
+
+
+class LuminanceInfo(C.Structure):    # ctl_luminance_info (Image::ComputeLuminanceInfo), 28 B
+    _fields_ = [("avg_color", C.c_float * 3), ("min_lum", C.c_float), ("max_lum", C.c_float), ("avg_lum", C.c_float),
+                ("avg_log_lum", C.c_float)]
+
 
 class PTParams(C.Structure):
     _fields_ = [("direct", C.c_int32), ("max_path_length", C.c_int32), ("rr_start_depth", C.c_int32),
@@ -297,6 +317,14 @@ SYMBOLS = [
     ("ctl_block_sampler_add_pass", C.c_int32, [_vp, _vp, C.c_uint32]),
     ("ctl_block_sampler_weights", C.c_int32, [_vp, _vp]),
     ("ctl_block_sampler_passes_done", C.c_int32, [_vp, _vp]),
+    ("ctl_image_pipeline", C.c_int32, [_vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32,
+                                       C.POINTER(ImageFilter), C.POINTER(Tonemap), _vp, _vp, _vp]),
+    ("ctl_image_luminance", C.c_int32, [_vp, _vp, C.c_uint32, C.c_uint32, C.POINTER(LuminanceInfo), _vp]),
+    ("ctl_filter_evaluate", C.c_int32, [C.POINTER(ImageFilter), C.c_float, C.c_float, C.POINTER(C.c_float)]),
+    ("ctl_rgbe_encode", C.c_int32, [C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
+    ("ctl_rgbe_decode", C.c_int32, [C.c_uint32, C.POINTER(C.c_float)]),
+    ("ctl_tonemap_constants", C.c_int32, [C.POINTER(Tonemap), C.c_float, C.c_float, C.POINTER(C.c_float),
+                                          C.POINTER(C.c_float)]),
 ]
 
 _lib = None

@@ -686,6 +686,7 @@ struct WfState {
 
 struct WptBuffers;
 struct AnimState;
+struct ImageState;
 
 // Device arrays of an uploaded scene (scene_dev.hip): one allocation per
 // KernelDynamicScene stream, reused by ctl_scene_update while it fits.
@@ -760,6 +761,7 @@ struct ctl_ctx {
     std::vector<void*> wf_allocs;
     ctl::WptBuffers* wpt = nullptr;             // WavefrontPathTracer queues (wpt.hip)
     ctl::AnimState* anim = nullptr;             // animated meshes, refit plans (anim.hip)
+    ctl::ImageState* img = nullptr;             // image pipeline scratch and NLM weights (pipeline.hip)
     uint64_t n_tri_data = 0, n_woop = 0, n_bvh_nodes = 0, n_scene_bvh = 0;   // uploaded array lengths
     int cu_count = 256;
     // Speculative DoPass windows (ctl_render_pass): the reference's host loop
@@ -815,6 +817,8 @@ void anim_free(ctl_ctx* c);
 // wpt.hip
 int wpt_pass(ctl_ctx* c, const ctl_wpt_params* p, ctl_pixel* fb, hipStream_t s);
 void wpt_free(ctl_ctx* c);
+// pipeline.hip
+void image_free(ctl_ctx* c);
 // ctl_trace.hip: the batch traversal launch and the ray counter, for wpt.hip
 // (rays, hits)[0, n) and, in the same launch, (rays2, hits2)[0, n2)
 int intersect_launch(ctl_ctx* c, int64_t n, const ctl_ray* rays, ctl_hit* hits, int32_t any_hit, hipStream_t s,

@@ -621,6 +621,7 @@ CTL_API void ctl_destroy(ctl_ctx* c) {
     ctl::wavefront_free(c);
     ctl::wpt_free(c);
     ctl::anim_free(c);
+    ctl::image_free(c);
     if (c->d_mt1) (void)hipFree(c->d_mt1);
     if (c->d_mt2) (void)hipFree(c->d_mt2);
     if (c->d_slices) (void)hipFree(c->d_slices);

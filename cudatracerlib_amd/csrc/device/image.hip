@@ -14,18 +14,12 @@
 
 #include "../../../include/ctl_trace.h"
 #include "common.h"
+#include "../ctl_image.h"
 
 namespace ctl {
 namespace {
 
-// toSRGBComponent (Math/Spectrum.cu:229-234)
-__device__ __forceinline__ float to_srgb(float v) {
-    if (v <= (float)0.0031308) return (float)12.92 * v;
-    return (float)1.055 * cr_pow(v, (float)(1.0 / 2.4)) - (float)0.055;
-}
-// SpectrumConverter::Float3ToCOLORREF (Math/Spectrum.h:521-526)
-__device__ __forceinline__ uint32_t to_u8(float x) { return (uint32_t)(unsigned char)(tmin(tmax(x, 0.0f), 1.0f) * 255.0f); }
-
+// to_srgb / to_u8: ../ctl_image.h
 __global__ __launch_bounds__(kBlock) void image_resolve_kernel(const ctl_pixel* fb, uint32_t n, float splat,
                                                                uint32_t* out) {
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;

@@ -49,7 +49,9 @@ extern "C" {
                                still 4, symbols added only: animated .xmsh (ctl_host_scene_write_animated_xmsh,
                                ctl_host_scene_set_animated_bvh, ctl_host_scene_add_animation / animation_*,
                                ctl_animation_frame_index) and resident animations (ctl_scene_set_animation,
-                               ctl_scene_animate_frame, ctl_scene_animate_time) */
+                               ctl_scene_animate_frame, ctl_scene_animate_time); the image pipeline
+                               (ctl_image_pipeline, ctl_image_luminance, ctl_filter_evaluate, ctl_rgbe_encode /
+                               decode, ctl_tonemap_constants) */
 
 #if defined(_WIN32)
 #define CTL_API __declspec(dllexport)
@@ -758,6 +760,92 @@ CTL_API ctl_status ctl_variance_add_pass(ctl_ctx* ctx, const ctl_pixel* d_fb, ui
  * (PixelVarianceBuffer.h:43-62) for n records; any output may be NULL. */
 CTL_API ctl_status ctl_variance_stats(ctl_ctx* ctx, const ctl_pixel_variance* d_var, uint64_t n, float* d_error,
                                       float* d_variance, float* d_average, void* stream);
+
+/* ---- image pipeline: filters, denoiser, tone map (Kernel/ImagePipeline) ---- */
+
+/* ctl_image_filter.type: the reference's Filter TYPE_FUNC ids (SceneTypes/
+ * Filter.h:28-171) run by CanonicalFilter, and the NonLocalMeansFilter. */
+enum { CTL_FILTER_BOX = 1, CTL_FILTER_GAUSSIAN = 2, CTL_FILTER_MITCHELL = 3,
+       CTL_FILTER_LANCZOS = 4, CTL_FILTER_TRIANGLE = 5,
+       CTL_FILTER_NLM = 16 };
+/* ctl_image_filter.flags.  CTL_NLM_DIRECT: the reference's kernel structure
+ * (49 patch taps per pixel pair, each with its own division) instead of the
+ * default, which evaluates every tap term once per workgroup and offset and
+ * shares it among the patches that contain it.  Both give the same bytes. */
+enum { CTL_NLM_DIRECT = 1u << 0 };
+typedef struct {                           /* 36 B */
+    uint32_t type;
+    float x_width, y_width;                /* canonical: FilterBase widths (box 1, gaussian 2, mitchell 2, lanczos 6, triangle 2) */
+    float a, b;                            /* gaussian: alpha = a (-2); mitchell: B = a, C = b (1/3, 1/3); lanczos: tau = a (3) */
+    float k, sigma2_scale;                 /* NLM: KEY_k (0.45), KEY_sigma2Scale (0.005) */
+    uint32_t update_periodicity;           /* NLM: KEY_UpdateWeightPeriodicity (25); 0 refused */
+    uint32_t flags;                        /* CTL_NLM_* */
+} ctl_image_filter;
+typedef struct { float key, burn; } ctl_tonemap;          /* ToneMapPostProcess: 0.18, 0 */
+typedef struct { float avg_color[3]; float min_lum, max_lum, avg_lum, avg_log_lum; } ctl_luminance_info; /* 28 B */
+
+/* applyImagePipeline (ImagePipeline.cu:54-84) into d_rgba[width*height]
+ * (RGBCOL as ctl_image_resolve writes it).  filter / process may be NULL:
+ *   neither        ctl_image_resolve
+ *   process only   copySamplesToFiltered, tone map, applyGammaCorrectureToOutput
+ *   filter only    filter, copyFilteredToOutput
+ *   both           filter, tone map, applyGammaCorrectureToOutput
+ * The three staged forms leave the filtered image, width*height RGBE words
+ * (one uint32 each: r, g, b, e from the low byte), in d_filtered, or in a
+ * scratch of the context when d_filtered is NULL.
+ * Canonical filters (CanonicalFilter.cu:6-36): the window [ceil(x - x_width),
+ * floor(x + x_width)] x [..y..] clipped to the image, rows outer.
+ * CTL_FILTER_NLM (NonLocalMeansFilter.cu, R = 6, F = 3) reads d_var, the
+ * ctl_pixel_variance records of the image (required for this type only), and
+ * keeps in the context what the reference's filter object keeps: the weights
+ * (169 floats per pixel, index (yo + 6) * 13 + (xo + 6)) and the num_passes of
+ * the last call.  The weights are recomputed when last + 1 != num_passes, when
+ * num_passes % update_periodicity == 0, or when the image size changed;
+ * otherwise the kept weights are applied to the current image.  With
+ * update_periodicity 1 no weight buffer exists: weights and apply run in one
+ * kernel.  The state lives until ctl_destroy; ctl_scene_upload does not reset
+ * it (it depends on the images of the calls only, as in the reference, where
+ * only Resize resets it).  Filter parameters other than the size do not
+ * trigger a recompute, as in the reference.
+ * The tone map (Reinhard05Kernel, ToneMapPostProcess.cu:6-38) takes its scale
+ * and white point from the luminance reduction of ctl_image_luminance, on the
+ * device.  Asynchronous on `stream`; device memory is (re)allocated only when
+ * an image is larger than any before.
+ * CTL_ERR_INVALID (with a message): an unknown type or flag bit; a canonical
+ * width <= 0, NaN or infinite; NLM without d_var, with update_periodicity 0 or
+ * a negative or NaN k / sigma2_scale; d_fb or d_rgba NULL with a non-empty
+ * image; width * height above 2^32 - 1.  An empty image is CTL_OK.  A failed
+ * weight allocation is CTL_ERR_NOMEM and resets the NLM state. */
+CTL_API ctl_status ctl_image_pipeline(ctl_ctx* ctx, const ctl_pixel* d_fb, const ctl_pixel_variance* d_var,
+                                      uint32_t width, uint32_t height, float splat_scale, uint32_t num_passes,
+                                      const ctl_image_filter* filter, const ctl_tonemap* process,
+                                      uint32_t* d_filtered, uint32_t* d_rgba, void* stream);
+
+/* Image::ComputeLuminanceInfo (Engine/Image.cu:88-168) of width*height RGBE
+ * words, with the semantics the reference intends: min_lum / max_lum are float
+ * minimum and maximum (max_lum from 0, min_lum from +infinity), the sums are
+ * divided by the pixel count, avg_log_lum = exp(mean(log(2.3e-5 + Y))).  The
+ * sums are taken in one fixed order (no float atomics): with n = width*height
+ * and G = min(ceil(n / 256), 1024) workgroups of 256 lanes, lane t of
+ * workgroup g adds pixels g*256 + t + j*G*256, j = 0, 1, ..., in that order;
+ * the 64 lanes of a wave are combined by the xor butterfly 32, 16, ..., 1; the
+ * four wave sums are added in wave order; then the G partials are summed the
+ * same way by one workgroup (lane t adds partials t, t + 256, ...).  So the
+ * result is a function of the image alone.  Synchronises `stream`. */
+CTL_API ctl_status ctl_image_luminance(ctl_ctx* ctx, const uint32_t* d_rgbe, uint32_t width, uint32_t height,
+                                       ctl_luminance_info* host_out, void* stream);
+
+/* Host helpers (no GPU): the building blocks above as the kernels compute them.
+ * Errors: CTL_ERR_INVALID, message from ctl_host_last_error. */
+/* Filter::Evaluate(x, y) of a canonical filter */
+CTL_API ctl_status ctl_filter_evaluate(const ctl_image_filter* filter, float x, float y, float* out);
+/* SpectrumConverter::Float3ToRGBE / RGBEToFloat3 (Math/Spectrum.h:534-565); a
+ * component converts to its byte by truncation saturated to 0..255, NaN -> 0 */
+CTL_API ctl_status ctl_rgbe_encode(const float rgb[3], uint32_t* out);
+CTL_API ctl_status ctl_rgbe_decode(uint32_t rgbe, float rgb[3]);
+/* ToneMapPostProcess::Apply's scale and 1 / Lwhite'^2 (ToneMapPostProcess.cu:26-38) */
+CTL_API ctl_status ctl_tonemap_constants(const ctl_tonemap* process, float avg_log_lum, float max_lum, float* scale,
+                                         float* inv_wp2);
 
 /* ---- adaptive sampling (Kernel/BlockSampler) ------------------------------ */
 
