@@ -374,6 +374,22 @@ def animation_frame_index(frame_rate, n_frames, t):
     return frame.value, lerp.value
 
 
+def woop_set(v0, v1, v2):
+    """TriIntersectorData::setData (ctl_woop_set) per triangle: v0, v1, v2 = (n, 3) float32
+    vertices (or one triangle's); returns the (n, 12) float32 Woop records."""
+    a = np.ascontiguousarray(v0, dtype=np.float32).reshape(-1, 3)
+    b = np.ascontiguousarray(v1, dtype=np.float32).reshape(-1, 3)
+    c = np.ascontiguousarray(v2, dtype=np.float32).reshape(-1, 3)
+    out = np.zeros((a.shape[0], 12), np.float32)
+    f = lib().ctl_woop_set
+    w = _abi.WoopTri()
+    pa, pb, pc, stride = a.ctypes.data, b.ctypes.data, c.ctypes.data, 12
+    for i in range(a.shape[0]):
+        f(pa + stride * i, pb + stride * i, pc + stride * i, C.byref(w))
+        out[i] = w.v[:]
+    return out
+
+
 def bvh_stack_bound(nodes, root_value=0):
     """(binary, 4-wide) worst-case traversal stack of a reference BVHNodeData
     tree (ctl_host_bvh_stack_bound); nodes = ctypes array / pointer of BVHNode."""
@@ -591,6 +607,27 @@ class Tracer:
         _check(self._L.ctl_scene_read(self._ctx, int(which), int(first), int(count), out.ctypes.data), self._ctx,
                "ctl_scene_read")
         return out
+
+    def array_size(self, which):
+        """Elements the device currently holds of a read_array array (ctl_scene_array_size):
+        the uploaded length plus, for the tree arrays, the regions rebuild_mesh appended."""
+        n = C.c_uint64(0)
+        _check(self._L.ctl_scene_array_size(self._ctx, int(which), C.byref(n)), self._ctx, "ctl_scene_array_size")
+        return int(n.value)
+
+    def rebuild_mesh(self, mesh, positions_ptr, n_tris, stream=0):
+        """Mesh::CompileMesh + ConstructBVH for resident geometry (ctl_scene_rebuild_mesh): mesh
+        `mesh`'s trees rebuilt on the device from positions_ptr = n_tris x 9 device floats
+        (v0 v1 v2 per triangle, the mesh's triangle order, object space)."""
+        _check(self._L.ctl_scene_rebuild_mesh(self._ctx, int(mesh), positions_ptr, int(n_tris), stream), self._ctx,
+               "ctl_scene_rebuild_mesh")
+
+    def last_rebuild_ms(self):
+        """Host milliseconds of the last rebuild_mesh's two phases (ctl_last_rebuild_ms): until the
+        build's first stream synchronisation, and from there to the end of the second."""
+        ms = (C.c_float * 2)()
+        _check(self._L.ctl_last_rebuild_ms(self._ctx, C.byref(ms)), self._ctx, "ctl_last_rebuild_ms")
+        return float(ms[0]), float(ms[1])
 
     def wide_trees(self, desc):
         """The uploaded scene's 4-wide trees as the device holds them (after any

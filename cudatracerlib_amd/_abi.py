@@ -44,7 +44,8 @@ CTL_DIRTY_TEXTURES, CTL_DIRTY_ENV, CTL_DIRTY_ALL = 256, 512, 1023
 (CTL_ARRAY_TRI_DATA, CTL_ARRAY_WOOP, CTL_ARRAY_BVH_NODES, CTL_ARRAY_SCENE_BVH, CTL_ARRAY_MESH_BOXES, CTL_ARRAY_RAY_EPS,
  CTL_ARRAY_SAMPLES_1D, CTL_ARRAY_SAMPLES_2D, CTL_ARRAY_NODE_XF, CTL_ARRAY_NODE_INV_XF, CTL_ARRAY_LIGHTS,
  CTL_ARRAY_LIGHT_TRIS, CTL_ARRAY_LIGHT_CDF, CTL_ARRAY_SCENE_BOX, CTL_ARRAY_ENV, CTL_ARRAY_WIDE_BVH,
- CTL_ARRAY_SCENE_WIDE_BVH, CTL_ARRAY_MESH_WIDE_BASE, CTL_ARRAY_CULL_BOUND) = range(19)
+ CTL_ARRAY_SCENE_WIDE_BVH, CTL_ARRAY_MESH_WIDE_BASE, CTL_ARRAY_CULL_BOUND, CTL_ARRAY_MESHES,
+ CTL_ARRAY_TRI_INDICES) = range(21)
 
 
 class BVHNode(C.Structure):          # BVHNodeData, 64 B
@@ -288,6 +289,9 @@ SYMBOLS = [
                                                      _vp, C.POINTER(Material), C.c_uint32]),
     ("ctl_scene_animate", C.c_int32, [_vp, C.c_uint32, _vp, _vp, C.c_uint32, C.c_float, _vp]),
     ("ctl_scene_read", C.c_int32, [_vp, C.c_uint32, C.c_uint64, C.c_uint64, _vp]),
+    ("ctl_scene_array_size", C.c_int32, [_vp, C.c_uint32, C.POINTER(C.c_uint64)]),
+    ("ctl_scene_rebuild_mesh", C.c_int32, [_vp, C.c_uint32, _vp, C.c_uint32, _vp]),
+    ("ctl_last_rebuild_ms", C.c_int32, [_vp, C.POINTER(C.c_float * 2)]),
     ("ctl_host_scene_add_xmsh", C.c_int32, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, C.c_uint32]),
     ("ctl_host_scene_write_xmsh", C.c_int32, [_vp, C.c_uint32, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     ("ctl_host_scene_write_animated_xmsh", C.c_int32, [_vp, C.c_uint32, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),

@@ -41,6 +41,7 @@
 
 #include <algorithm>
 #include <cfloat>
+#include <chrono>
 #include <cmath>
 #include <cstring>
 
@@ -119,6 +120,7 @@ struct AnimState {
     size_t bones_cap = 0;
     uint32_t n_meshes = 0, n_nodes = 0;
     std::vector<uint32_t> node_mesh;    // Node::m_uMeshIndex per node
+    std::vector<uint32_t> node_lights;  // Node::m_uLights.size() per node
     std::vector<void*> allocs;
 };
 
@@ -990,7 +992,10 @@ int anim_setup(ctl_ctx* c, const ctl_scene_desc* d, const std::vector<WideNode>&
     auto fail = [&](const std::string& m) { c->err = "scene_upload: " + m; anim_free(c); return (int)CTL_ERR_INVALID; };
     A->n_meshes = d->n_meshes;
     A->n_nodes = d->n_nodes;
-    for (uint32_t i = 0; i < d->n_nodes; i++) A->node_mesh.push_back(d->nodes[i].mesh_index);
+    for (uint32_t i = 0; i < d->n_nodes; i++) {
+        A->node_mesh.push_back(d->nodes[i].mesh_index);
+        A->node_lights.push_back(d->nodes[i].num_lights);
+    }
     if (!anim_upload(A, &A->d_mesh_boxes, d->mesh_boxes, 6ull * d->n_meshes) ||
         !anim_alloc(A, &A->d_inst_boxes, 6ull * std::max(1u, d->n_nodes)) || !anim_alloc(A, &A->d_eps, 10) ||
         hipHostMalloc((void**)&A->h_eps, (10 + 6ull * std::max(1u, d->n_nodes)) * sizeof(float), hipHostMallocDefault) !=
@@ -1273,28 +1278,36 @@ CTL_API ctl_status ctl_scene_set_transform(ctl_ctx* c, uint32_t node, const ctl_
     return scene_after_move(c, std::vector<uint32_t>{node}, s, "scene_set_transform");
 }
 
-CTL_API ctl_status ctl_scene_read(ctl_ctx* c, uint32_t array, uint64_t first, uint64_t count, void* dst) {
-    if (!c || (!dst && count)) return CTL_ERR_INVALID;
+// A ctl_scene_read array: its device address (or host_src for the values the
+// context keeps on the host), element size and the elements the device holds.
+struct ReadArray {
+    const void* src = nullptr;
+    const void* host_src = nullptr;
+    size_t elem = 0;
+    uint64_t n = 0;
+};
+static ctl_status read_array(ctl_ctx* c, uint32_t array, ReadArray& R) {
     if (!c->has_scene && array != CTL_ARRAY_SAMPLES_1D && array != CTL_ARRAY_SAMPLES_2D) {
         c->err = "scene_read: no scene uploaded";
         return CTL_ERR_STATE;
     }
     const DevScene& S = c->scene;
-    const void* src = nullptr;
-    size_t elem = 0;
-    uint64_t n = 0;
+    const void*& src = R.src;
+    size_t& elem = R.elem;
+    uint64_t& n = R.n;
     switch (array) {
         case CTL_ARRAY_TRI_DATA: src = S.tri_data; elem = sizeof(ctl_triangle_data); n = c->n_tri_data; break;
-        case CTL_ARRAY_WOOP: src = S.woop; elem = sizeof(ctl_woop_tri); n = c->n_woop; break;
-        case CTL_ARRAY_BVH_NODES: src = S.bvh; elem = sizeof(ctl_bvh_node); n = c->n_bvh_nodes; break;
+        // the tree arrays: the uploaded lengths plus the regions ctl_scene_rebuild_mesh appended
+        case CTL_ARRAY_WOOP: src = S.woop; elem = sizeof(ctl_woop_tri); n = c->n_woop + c->extra_entries; break;
+        case CTL_ARRAY_BVH_NODES: src = S.bvh; elem = sizeof(ctl_bvh_node); n = c->n_bvh_nodes + c->extra_nodes; break;
+        case CTL_ARRAY_TRI_INDICES:
+            src = S.tri_idx; elem = sizeof(ctl_tri_index); n = c->sarr[SA_IDX].bytes / elem + c->extra_entries; break;
+        case CTL_ARRAY_MESHES: src = S.meshes; elem = sizeof(ctl_kernel_mesh); n = c->sarr[SA_MESHES].bytes / elem; break;
         case CTL_ARRAY_SCENE_BVH: src = S.scene_bvh; elem = sizeof(ctl_bvh_node); n = c->n_scene_bvh; break;
         case CTL_ARRAY_MESH_BOXES:
             if (!c->anim) { c->err = "scene_read: the scene had no mesh boxes"; return CTL_ERR_STATE; }
             src = c->anim->d_mesh_boxes; elem = 6 * sizeof(float); n = c->anim->n_meshes; break;
-        case CTL_ARRAY_RAY_EPS:
-            if (first != 0 || count > 1) { c->err = "scene_read: ray eps is one value"; return CTL_ERR_INVALID; }
-            if (count) memcpy(dst, &S.ray_eps, sizeof(float));
-            return CTL_OK;
+        case CTL_ARRAY_RAY_EPS: R.host_src = &S.ray_eps; elem = sizeof(float); n = 1; break;
         case CTL_ARRAY_SAMPLES_1D:
         case CTL_ARRAY_SAMPLES_2D:
             if (c->active < 0) { c->err = "scene_read: no sampler tables (call ctl_sampler_generate)"; return CTL_ERR_STATE; }
@@ -1310,10 +1323,7 @@ CTL_API ctl_status ctl_scene_read(ctl_ctx* c, uint32_t array, uint64_t first, ui
         case CTL_ARRAY_SCENE_BOX:
             if (!c->anim || !c->device_eps) { c->err = "scene_read: the scene box is derived by set_transform / animate"; return CTL_ERR_STATE; }
             src = c->anim->d_eps; elem = 6 * sizeof(float); n = 1; break;
-        case CTL_ARRAY_CULL_BOUND:
-            if (first != 0 || count > 1) { c->err = "scene_read: the cull bound is one record of 3 floats"; return CTL_ERR_INVALID; }
-            if (count) memcpy(dst, S.cull_m, 3 * sizeof(float));
-            return CTL_OK;
+        case CTL_ARRAY_CULL_BOUND: R.host_src = S.cull_m; elem = 3 * sizeof(float); n = 1; break;
         case CTL_ARRAY_ENV:
             if (!S.env) { c->err = "scene_read: no environment light"; return CTL_ERR_STATE; }
             src = S.env; elem = sizeof(ctl_env_light); n = 1; break;
@@ -1325,16 +1335,214 @@ CTL_API ctl_status ctl_scene_read(ctl_ctx* c, uint32_t array, uint64_t first, ui
             src = array == CTL_ARRAY_WIDE_BVH ? (const void*)S.wbvh
                   : array == CTL_ARRAY_SCENE_WIDE_BVH ? (const void*)S.scene_wbvh : (const void*)S.mesh_wbase;
             n = c->sarr[array == CTL_ARRAY_WIDE_BVH ? SA_WBVH : array == CTL_ARRAY_SCENE_WIDE_BVH ? SA_SWBVH : SA_WBASE].bytes / elem;
+            if (array == CTL_ARRAY_WIDE_BVH) n += c->extra_wide;
             break;
         default: c->err = "scene_read: unknown array"; return CTL_ERR_INVALID;
     }
-    if (first > n || count > n - first) { c->err = "scene_read: range out of bounds"; return CTL_ERR_INVALID; }
+    return CTL_OK;
+}
+
+CTL_API ctl_status ctl_scene_read(ctl_ctx* c, uint32_t array, uint64_t first, uint64_t count, void* dst) {
+    if (!c || (!dst && count)) return CTL_ERR_INVALID;
+    ReadArray R;
+    const ctl_status r = read_array(c, array, R);
+    if (r != CTL_OK) return r;
+    if (R.host_src) {
+        if (first != 0 || count > 1) {
+            c->err = array == CTL_ARRAY_RAY_EPS ? "scene_read: ray eps is one value"
+                                                : "scene_read: the cull bound is one record of 3 floats";
+            return CTL_ERR_INVALID;
+        }
+        if (count) memcpy(dst, R.host_src, R.elem);
+        return CTL_OK;
+    }
+    if (first > R.n || count > R.n - first) { c->err = "scene_read: range out of bounds"; return CTL_ERR_INVALID; }
     if (!count) return CTL_OK;
     if (hipSetDevice(c->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
-        hipMemcpy(dst, (const char*)src + first * elem, count * elem, hipMemcpyDeviceToHost) != hipSuccess) {
+        hipMemcpy(dst, (const char*)R.src + first * R.elem, count * R.elem, hipMemcpyDeviceToHost) != hipSuccess) {
         c->err = "scene_read: copy failed";
         return CTL_ERR_HIP;
     }
+    return CTL_OK;
+}
+
+CTL_API ctl_status ctl_scene_array_size(ctl_ctx* c, uint32_t array, uint64_t* count) {
+    if (!c || !count) return CTL_ERR_INVALID;
+    ReadArray R;
+    const ctl_status r = read_array(c, array, R);
+    if (r != CTL_OK) return r;
+    *count = R.n;
+    return CTL_OK;
+}
+
+// ---------------------------------------------------------------------------
+// ctl_scene_rebuild_mesh: a static mesh's trees rebuilt by lbvh.hip
+// ---------------------------------------------------------------------------
+
+// Array slot `a` grown to hold `elems` elements of `elem` bytes plus `pad` zeroed
+// bytes, its contents kept (the device drains first: kernels on any stream may
+// read the old allocation).  sarr[].bytes stays the uploaded length.
+static ctl_status grow_array(ctl_ctx* c, int a, uint64_t elems, size_t elem, size_t pad, uint64_t held) {
+    SceneArray& A = c->sarr[a];
+    const size_t need = (size_t)elems * elem + pad;
+    if (A.cap >= need) return CTL_OK;
+    void* p = nullptr;
+    if (hipDeviceSynchronize() != hipSuccess) { c->err = "scene_rebuild_mesh: device synchronisation failed"; return CTL_ERR_HIP; }
+    if (hipMalloc(&p, need) != hipSuccess) {
+        c->err = "scene_rebuild_mesh: hipMalloc of " + std::to_string(need) + " bytes failed";
+        return CTL_ERR_NOMEM;
+    }
+    const size_t keep = std::min<size_t>((size_t)held * elem, A.cap);
+    if (hipMemset(p, 0, need) != hipSuccess || (keep && hipMemcpy(p, A.p, keep, hipMemcpyDeviceToDevice) != hipSuccess)) {
+        (void)hipFree(p);
+        c->err = "scene_rebuild_mesh: copy of the scene arrays failed";
+        return CTL_ERR_HIP;
+    }
+    if (A.p) (void)hipFree(A.p);
+    A.p = p;
+    A.cap = need;
+    return CTL_OK;
+}
+
+// the mesh's record, wide base and local box switched to the region just built
+__global__ void mesh_switch_kernel(ctl_kernel_mesh* meshes, uint32_t* wbase, float* mesh_boxes, uint32_t mesh,
+                                   ctl_kernel_mesh rec, uint32_t wide_base, const uint32_t* res) {
+    meshes[mesh] = rec;
+    if (wbase) wbase[mesh] = wide_base;
+    for (int k = 0; k < 6; k++) mesh_boxes[6 * mesh + k] = __uint_as_float(res[9 + k]);
+}
+
+CTL_API ctl_status ctl_scene_rebuild_mesh(ctl_ctx* c, uint32_t mesh, const float* d_positions, uint32_t n_tris,
+                                          void* stream) {
+    if (!c) return CTL_ERR_INVALID;
+    auto refuse = [&](const char* m) { c->err = std::string("scene_rebuild_mesh: ") + m; return (ctl_status)CTL_ERR_INVALID; };
+    if (!c->has_scene || !c->anim) return refuse("no scene uploaded (or one without mesh boxes)");
+    AnimState* A = c->anim;
+    DevScene& S = c->scene;
+    if (mesh >= c->h_meshes.size() || mesh >= A->n_meshes) return refuse("mesh index out of range");
+    if (!d_positions) return refuse("positions are NULL");
+    // the mesh's triangles: up to the next mesh's first one
+    const uint32_t t0 = c->h_meshes[mesh].triangle_offset;
+    uint64_t t1 = c->n_tri_data;
+    for (const ctl_kernel_mesh& m : c->h_meshes)
+        if (m.triangle_offset > t0) t1 = std::min<uint64_t>(t1, m.triangle_offset);
+    if (n_tris == 0 || n_tris != t1 - t0) return refuse("n_tris differs from the mesh's triangle count");
+    // the fit's record buffer (32 B per node) is addressed with 32-bit byte offsets below 2^31
+    if (n_tris > (1u << 26)) return refuse("a mesh of more than 2^26 triangles");
+    for (const AnimMeshPlan& P : A->meshes)
+        if (P.am.mesh == mesh) return refuse("an animated mesh is rebuilt by ctl_scene_animate");
+    std::vector<uint32_t> moved;
+    for (uint32_t i = 0; i < A->n_nodes; i++) {
+        if (A->node_mesh[i] != mesh) continue;
+        if (A->node_lights[i]) return refuse("a node of the mesh carries an area light (its ShapeSet reads the mesh's Woop records)");
+        moved.push_back(i);
+    }
+    if (c->tree_flags & CTL_SCENE_WIDE_QUANT) return refuse("64-B quantized trees are not rebuilt (upload without CTL_SCENE_WIDE_QUANT)");
+    if (hipSetDevice(c->device) != hipSuccess) { c->err = "scene_rebuild_mesh: hipSetDevice failed"; return CTL_ERR_HIP; }
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const bool wide = S.wide != 0;
+    const uint32_t nn = std::max(n_tris - 1, 1u);   // binary nodes, and the most wide nodes
+    // the first rebuild of the mesh: two regions past what the arrays hold (one entry
+    // kept between the uploaded Woop / index records and the first region: the zeroed
+    // look-ahead entry an upload of those arrays rewrites), the scratch
+    if (c->regions.size() < c->h_meshes.size()) c->regions.resize(c->h_meshes.size());
+    MeshRegion& G = c->regions[mesh];
+    if (!G.has) {
+        const uint64_t up_nodes = c->n_bvh_nodes, up_entries = c->sarr[SA_IDX].bytes / sizeof(ctl_tri_index),
+                       up_woop = c->n_woop, up_wide = wide ? c->sarr[SA_WBVH].bytes / sizeof(WideNode) : 0;
+        const uint64_t gap = c->extra_entries ? 0 : 1;
+        MeshRegion R;
+        for (int k = 0; k < 2; k++) {
+            R.node0[k] = up_nodes + c->extra_nodes + (uint64_t)k * nn;
+            R.entry0[k] = up_entries + c->extra_entries + gap + (uint64_t)k * n_tris;
+            R.wide0[k] = up_wide + c->extra_wide + (uint64_t)k * nn;
+        }
+        if (up_woop != up_entries) return refuse("the scene's Woop and index arrays differ in length");
+        if (R.entry0[1] + n_tris >= kWideLeafMaxEntry || 4 * (R.node0[1] + nn) > 0x7fffffffull)
+            return refuse("the scene arrays would pass the offsets a tree can address");
+        ctl_status r;
+        const uint64_t ne = c->extra_nodes + 2ull * nn, ee = c->extra_entries + gap + 2ull * n_tris, we = c->extra_wide + 2ull * nn;
+        if ((r = (ctl_status)lbvh_reserve(c, n_tris)) != CTL_OK ||
+            (r = grow_array(c, SA_BVH, up_nodes + ne, sizeof(ctl_bvh_node), 0, up_nodes + c->extra_nodes)) != CTL_OK ||
+            (r = grow_array(c, SA_WOOP, up_woop + ee, sizeof(ctl_woop_tri), sizeof(ctl_woop_tri), up_woop + c->extra_entries + 1)) != CTL_OK ||
+            (r = grow_array(c, SA_IDX, up_entries + ee, sizeof(ctl_tri_index), sizeof(ctl_tri_index), up_entries + c->extra_entries + 1)) != CTL_OK ||
+            (wide && (r = grow_array(c, SA_WBVH, up_wide + we, sizeof(WideNode), 0, up_wide + c->extra_wide)) != CTL_OK))
+            return r;
+        S.bvh = reinterpret_cast<const float4*>(c->sarr[SA_BVH].p);
+        S.woop = reinterpret_cast<const float4*>(c->sarr[SA_WOOP].p);
+        S.tri_idx = reinterpret_cast<const uint32_t*>(c->sarr[SA_IDX].p);
+        if (wide) S.wbvh = reinterpret_cast<const float4*>(c->sarr[SA_WBVH].p);
+        c->extra_nodes = ne;
+        c->extra_entries = ee;
+        if (wide) c->extra_wide = we;
+        c->scene_epoch++;   // the arrays moved: a pending render-ahead window read the old ones
+        R.has = true;
+        G = R;
+    } else {
+        const ctl_status r = (ctl_status)lbvh_reserve(c, n_tris);
+        if (r != CTL_OK) return r;
+    }
+    const int t = G.cur == 0 ? 1 : 0;   // the region the mesh is not using
+    const auto clk0 = std::chrono::steady_clock::now();
+    float* nodes = reinterpret_cast<float*>(c->sarr[SA_BVH].p) + 16 * G.node0[t];
+    float* woop = reinterpret_cast<float*>(c->sarr[SA_WOOP].p) + 12 * G.entry0[t];
+    uint32_t* idx = reinterpret_cast<uint32_t*>(c->sarr[SA_IDX].p) + G.entry0[t];
+    WideNode* wn = wide ? reinterpret_cast<WideNode*>(c->sarr[SA_WBVH].p) + G.wide0[t] : nullptr;
+    ctl_status r = (ctl_status)lbvh_build(c, d_positions, n_tris, nodes, woop, idx, wn, s);
+    if (r != CTL_OK) return r;
+    if (hipStreamSynchronize(s) != hipSuccess) { c->err = "scene_rebuild_mesh: build failed"; return CTL_ERR_HIP; }
+    const auto clk1 = std::chrono::steady_clock::now();
+    const uint32_t* res = lbvh_result(c);
+    if (res[6]) return refuse("non-finite position");
+    // the traversal stacks with this mesh's new trees (scene_dev.hip commit)
+    const int bin = n_tris == 1 ? 1 : 1 + (int)res[8], wid = wide ? (int)res[7] : 0;
+    int mesh_bin = bin, mesh_wide = wid;
+    for (size_t m = 0; m < c->mesh_bin_bound.size(); m++)
+        if (m != mesh) {
+            mesh_bin = std::max(mesh_bin, c->mesh_bin_bound[m]);
+            mesh_wide = std::max(mesh_wide, c->mesh_wide_bound[m]);
+        }
+    int bound = std::max(mesh_bin, mesh_wide);
+    if (c->stack_top_bin >= 0)
+        bound = std::max(c->stack_top_bin + 1 + mesh_bin, c->stack_top_wide >= 0 ? c->stack_top_wide + 1 + mesh_wide : 0);
+    if (bound > kStackMax) return refuse("the new BVH needs a deeper traversal stack than the traversal has");
+    // the switch
+    ctl_kernel_mesh rec = c->h_meshes[mesh];
+    rec.bvh_node_offset = (uint32_t)(4 * G.node0[t]);
+    rec.bvh_triangle_offset = (uint32_t)(3 * G.entry0[t]);
+    rec.bvh_indices_offset = (uint32_t)G.entry0[t];
+    hipLaunchKernelGGL(mesh_switch_kernel, dim3(1), dim3(1), 0, s, const_cast<ctl_kernel_mesh*>(S.meshes),
+                       wide ? const_cast<uint32_t*>(S.mesh_wbase) : nullptr, A->d_mesh_boxes, mesh, rec,
+                       (uint32_t)G.wide0[t], lbvh_result_dev(c));
+    if (hipGetLastError() != hipSuccess) { c->err = "scene_rebuild_mesh: launch failed"; return CTL_ERR_HIP; }
+    G.cur = t;
+    if (mesh < c->mesh_bin_bound.size()) { c->mesh_bin_bound[mesh] = bin; c->mesh_wide_bound[mesh] = wid; }
+    c->stack_mesh_bin = mesh_bin;
+    c->stack_mesh_wide = mesh_wide;
+    c->stack_bound = bound;
+    if (wide && mesh < c->h_wbase.size()) c->h_wbase[mesh] = (uint32_t)G.wide0[t];
+    if (S.single && S.n_nodes > 0 && A->node_mesh[~(uint32_t)S.start_node] == mesh) {
+        S.s_node_base = rec.bvh_node_offset;
+        S.s_tri_base = rec.bvh_triangle_offset;
+        S.s_idx_base = rec.bvh_indices_offset;
+        S.s_wnode_base = wide ? (uint32_t)G.wide0[t] : 0;
+    }
+    c->scene_epoch++;   // the geometry moves (render-ahead passes are dropped)
+    c->device_edited = true;
+    // instances of the mesh, the instance tree, scene box, epsilon, cull bound, environment sphere
+    ctl_status r2 = CTL_OK;
+    if (A->n_nodes) r2 = scene_after_move(c, moved, s, "scene_rebuild_mesh");
+    else if (hipStreamSynchronize(s) != hipSuccess) { c->err = "scene_rebuild_mesh: switch failed"; r2 = CTL_ERR_HIP; }
+    const auto clk2 = std::chrono::steady_clock::now();
+    c->rebuild_ms[0] = std::chrono::duration<float, std::milli>(clk1 - clk0).count();
+    c->rebuild_ms[1] = std::chrono::duration<float, std::milli>(clk2 - clk1).count();
+    return r2;
+}
+
+CTL_API ctl_status ctl_last_rebuild_ms(ctl_ctx* c, float ms[2]) {
+    if (!c || !ms) return CTL_ERR_INVALID;
+    ms[0] = c->rebuild_ms[0];
+    ms[1] = c->rebuild_ms[1];
     return CTL_OK;
 }
 

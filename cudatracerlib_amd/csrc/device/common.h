@@ -687,6 +687,16 @@ struct WfState {
 struct WptBuffers;
 struct AnimState;
 struct ImageState;
+struct LbvhScratch;
+
+// The two regions ctl_scene_rebuild_mesh appended to the node, Woop, index and
+// 4-wide arrays for one mesh (anim.hip): each rebuild builds into the one the
+// mesh is not using.  Element offsets into the device arrays.
+struct MeshRegion {
+    bool has = false;
+    int cur = -1;                               // the region the mesh's record points to (-1: the uploaded range)
+    uint64_t node0[2] = {0, 0}, entry0[2] = {0, 0}, wide0[2] = {0, 0};
+};
 
 // Device arrays of an uploaded scene (scene_dev.hip): one allocation per
 // KernelDynamicScene stream, reused by ctl_scene_update while it fits.
@@ -762,6 +772,15 @@ struct ctl_ctx {
     ctl::WptBuffers* wpt = nullptr;             // WavefrontPathTracer queues (wpt.hip)
     ctl::AnimState* anim = nullptr;             // animated meshes, refit plans (anim.hip)
     ctl::ImageState* img = nullptr;             // image pipeline scratch and NLM weights (pipeline.hip)
+    // ctl_scene_rebuild_mesh: the builder's scratch (lbvh.hip), the regions appended past
+    // the uploaded arrays (elements; the uploaded lengths stay in sarr[].bytes), a host copy
+    // of the uploaded mesh records and the per-mesh stack bounds behind stack_mesh_*
+    ctl::LbvhScratch* lbvh = nullptr;
+    std::vector<ctl::MeshRegion> regions;
+    uint64_t extra_nodes = 0, extra_entries = 0, extra_wide = 0;
+    std::vector<ctl_kernel_mesh> h_meshes;
+    std::vector<int> mesh_bin_bound, mesh_wide_bound;
+    float rebuild_ms[2] = {0.0f, 0.0f};         // host time of the last rebuild's two phases (ctl_last_rebuild_ms)
     uint64_t n_tri_data = 0, n_woop = 0, n_bvh_nodes = 0, n_scene_bvh = 0;   // uploaded array lengths
     int cu_count = 256;
     // Speculative DoPass windows (ctl_render_pass): the reference's host loop
@@ -814,6 +833,14 @@ struct WideNode;
 int anim_setup(ctl_ctx* c, const ctl_scene_desc* d, const std::vector<WideNode>& wn, const std::vector<uint32_t>& wbase,
                const std::vector<WideNode>& sw);
 void anim_free(ctl_ctx* c);
+// lbvh.hip: the device mesh builder behind ctl_scene_rebuild_mesh
+constexpr uint32_t kLbvhResWords = 16;   // [6] non-finite flag [7] wide stack bound [8] root height [9..14] mesh box
+int lbvh_reserve(ctl_ctx* c, uint32_t n);
+int lbvh_build(ctl_ctx* c, const float* d_pos, uint32_t n, void* nodes, void* woop, uint32_t* idx, void* wide,
+               hipStream_t s);
+const uint32_t* lbvh_result(const ctl_ctx* c);
+const uint32_t* lbvh_result_dev(const ctl_ctx* c);
+void lbvh_free(ctl_ctx* c);
 // wpt.hip
 int wpt_pass(ctl_ctx* c, const ctl_wpt_params* p, ctl_pixel* fb, hipStream_t s);
 void wpt_free(ctl_ctx* c);

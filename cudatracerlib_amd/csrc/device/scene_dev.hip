@@ -244,7 +244,10 @@ ctl_status commit_arrays(ctl_ctx* c, const ctl_scene_desc* d, uint32_t dirty, hi
     // after set_transform / animate, re-uploading any tree group returns every
     // device-edited array to the desc (geometry, instances, their area lights,
     // the environment's scene sphere), never a mix of moved and unmoved state
-    if (c->device_edited && (dirty & (kDirtyTrees | CTL_DIRTY_TRI_INDICES | CTL_DIRTY_MESHES)))
+    // (a mesh rebuilt by ctl_scene_rebuild_mesh lives in a region past the uploaded
+    // Woop records: an upload of those alone returns it to the desc as well)
+    const bool regions_used = c->extra_nodes != 0;
+    if (c->device_edited && (dirty & (kDirtyTrees | CTL_DIRTY_TRI_INDICES | CTL_DIRTY_MESHES | (regions_used ? CTL_DIRTY_WOOP : 0u))))
         dirty |= kDirtyTrees | CTL_DIRTY_TRI_INDICES | CTL_DIRTY_MESHES | CTL_DIRTY_TRI_DATA | CTL_DIRTY_WOOP |
                  CTL_DIRTY_LIGHTS | CTL_DIRTY_ENV;
     ctl_status r;
@@ -298,11 +301,14 @@ ctl_status commit_arrays(ctl_ctx* c, const ctl_scene_desc* d, uint32_t dirty, hi
     try {
         if (mesh_trees) {
             c->h_wbase.assign(d->n_meshes, 0);
+            c->mesh_bin_bound.assign(d->n_meshes, 0);
+            c->mesh_wide_bound.assign(d->n_meshes, 0);
             int mesh_bin = 0, mesh_wide = 0;
             for (uint32_t m = 0; m < d->n_meshes && d->n_bvh_nodes > 0; m++) {
                 const size_t first = d->meshes[m].bvh_node_offset / 4;
                 if (first >= d->n_bvh_nodes) throw std::runtime_error("mesh BVH offset out of range");
-                mesh_bin = std::max(mesh_bin, binary_stack_bound(d->bvh_nodes + first, d->n_bvh_nodes - first, 0, kStackMax));
+                c->mesh_bin_bound[m] = binary_stack_bound(d->bvh_nodes + first, d->n_bvh_nodes - first, 0, kStackMax);
+                mesh_bin = std::max(mesh_bin, c->mesh_bin_bound[m]);
                 if (!wide) continue;
                 c->h_wbase[m] = (uint32_t)wn.size();
                 // the mesh's entries start at bvh_indices_offset (meshes may be stored in any
@@ -311,7 +317,8 @@ ctl_status commit_arrays(ctl_ctx* c, const ctl_scene_desc* d, uint32_t dirty, hi
                 if (e0 > d->n_tri_indices) throw std::runtime_error("mesh entry offset out of range");
                 collapse_wide(d->bvh_nodes + first, d->n_bvh_nodes - first, 0, wn, nullptr, d->tri_indices + e0,
                               (size_t)(d->n_tri_indices - e0));
-                mesh_wide = std::max(mesh_wide, wide_stack_bound(wn.data() + c->h_wbase[m], wn.size() - c->h_wbase[m], 0, kStackMax));
+                c->mesh_wide_bound[m] = wide_stack_bound(wn.data() + c->h_wbase[m], wn.size() - c->h_wbase[m], 0, kStackMax);
+                mesh_wide = std::max(mesh_wide, c->mesh_wide_bound[m]);
             }
             c->stack_mesh_bin = mesh_bin;
             c->stack_mesh_wide = mesh_wide;
@@ -450,6 +457,13 @@ ctl_status commit_arrays(ctl_ctx* c, const ctl_scene_desc* d, uint32_t dirty, hi
         SD_HIP(c, hipStreamSynchronize(s));
     }
     c->n_anim_meshes = d->n_anim_meshes;
+    if (dirty & (kDirtyTrees | CTL_DIRTY_TRI_INDICES | CTL_DIRTY_MESHES)) {
+        // every mesh is back in its uploaded range: the regions of ctl_scene_rebuild_mesh
+        // are not part of the desc (their allocations stay for the next rebuild)
+        c->regions.clear();
+        c->extra_nodes = c->extra_entries = c->extra_wide = 0;
+        c->h_meshes.assign(d->meshes, d->meshes + d->n_meshes);
+    }
     if (dirty & CTL_DIRTY_NODES) c->device_edited = false;
     return CTL_OK;
 }
@@ -462,6 +476,10 @@ void free_scene(ctl_ctx* c) {
     c->spec.pending = false;
     free_arrays(c);
     anim_free(c);
+    lbvh_free(c);
+    c->regions.clear();
+    c->extra_nodes = c->extra_entries = c->extra_wide = 0;
+    c->h_meshes.clear();
     c->has_scene = false;
     c->h_wbase.clear();
     c->tree_flags = 0xffffffffu;

@@ -655,9 +655,86 @@ enum {
      * scene box and mesh boxes of the desc, and of the device after
      * set_transform / animate (an animated mesh's boxes are kept in it until
      * its tree is uploaded again).                                           */
-    CTL_ARRAY_CULL_BOUND = 18
+    CTL_ARRAY_CULL_BOUND = 18,
+    CTL_ARRAY_MESHES = 19,      /* ctl_kernel_mesh: after ctl_scene_rebuild_mesh a mesh's offsets
+                                   name the region its trees were built into             */
+    CTL_ARRAY_TRI_INDICES = 20  /* ctl_tri_index       */
 };
+/* Every array is bounded by what the device holds: the node, Woop, index and
+ * 4-wide arrays by the uploaded length plus the regions ctl_scene_rebuild_mesh
+ * appended (ctl_scene_array_size). */
 CTL_API ctl_status ctl_scene_read(ctl_ctx* ctx, uint32_t array, uint64_t first, uint64_t count, void* host_dst);
+/* Elements the device currently holds of a ctl_scene_read array. */
+CTL_API ctl_status ctl_scene_array_size(ctl_ctx* ctx, uint32_t array, uint64_t* count);
+
+/* ---- device BVH build for resident geometry ------------------------------ */
+
+/* Mesh::CompileMesh + ConstructBVH (Engine/Mesh.cpp) for geometry already on
+ * the device: rebuilds mesh `mesh` of the uploaded scene from new triangle
+ * positions, d_positions = n_tris x 9 floats (v0 v1 v2 of triangle i, in the
+ * mesh's triangle order, object space, device memory).  n_tris must equal the
+ * mesh's triangle count: triangle i keeps TriangleData i, its material and its
+ * global index.  TriangleData is not touched: a caller whose shading normals
+ * move sends them with ctl_scene_update(CTL_DIRTY_TRI_DATA).
+ *
+ * The trees are an LBVH (Karras 2012; csrc/device/lbvh.hip states every step,
+ * tests/lbvh_ref.py restates it on the CPU): 63-bit Morton keys of the boxes'
+ * lo + hi inside their own box, a stable radix sort, leaves of one triangle.
+ * Every step is a function of the positions alone, so the same positions give
+ * the same bytes on every call, context and rank.  The call writes, for the
+ * mesh: one Woop record per triangle in the new leaf order, one
+ * TriIntersectorData2 word per triangle ((tri << 1) | 1), the binary
+ * BVHNodeData tree in the reference layout (root at node 0, child and parent
+ * words as the host builders write them; a one-triangle mesh is node 0 with a
+ * leaf and the 0x76543210 child), unless the scene is CTL_SCENE_BINARY_BVH the
+ * 4-wide copy (a greedy collapse: open the inner child of largest surface area
+ * until four children, a tie to the lowest slot, the opened slot taking its
+ * child 0 and the first free slot its child 1; wide nodes numbered by an
+ * exclusive prefix sum, over the binary node index, of "this binary node starts
+ * a wide node", so the wide root is the region's first node; counted leaf
+ * codes, quiet-NaN boxes and 0x76543210 in empty slots, a zero pad), and the
+ * mesh's local box.  It then refreshes, for
+ * every node that instantiates the mesh, what ctl_scene_animate refreshes: the
+ * instance boxes, the instance tree and its 4-wide copy, the scene box, ray
+ * epsilon and cull bound, the environment light's scene sphere; a pending
+ * CTL_PT_RENDER_AHEAD window is dropped.
+ *
+ * Storage: the new trees do not fit the uploaded ranges in general, so the
+ * first rebuild of a mesh appends two regions to the node, Woop, index and
+ * 4-wide device arrays, each sized for n_tris (max(n_tris - 1, 1) binary nodes,
+ * as many 4-wide nodes, n_tris entries).  That append reallocates the arrays
+ * once (it synchronises the device; the contents are kept) and leaves the
+ * mesh's uploaded range unused.  Every rebuild builds into the region the mesh
+ * is not using and switches the mesh's record (CTL_ARRAY_MESHES) and 4-wide
+ * base to it only after the checks below pass, so a refused call leaves the
+ * scene as it was.  The regions are not part of the desc: ctl_scene_update
+ * keeps comparing clean arrays against the uploaded lengths, and an update of
+ * a tree group (BVH, nodes, indices, meshes; or the Woop records once a region
+ * exists) returns the mesh to the desc's trees together with every other
+ * device-edited array, as after ctl_scene_animate.
+ *
+ * CTL_ERR_INVALID, with the context usable and no render error pending: no
+ * scene, `mesh` out of range, n_tris 0 or not the mesh's count, NULL
+ * positions, more than 2^26 triangles, an animated mesh (ctl_scene_animate
+ * rebuilds it), a mesh one of
+ * whose nodes carries an area light (its ShapeSet reads the mesh's Woop
+ * records), a CTL_SCENE_WIDE_QUANT scene, a non-finite position (flagged by
+ * the first kernel, read before the switch), new trees whose traversal stack
+ * bound, combined with the instance tree's as at upload, passes the
+ * traversal's stack; on success ctl_scene_stack_bound reports the new bound.
+ *
+ * Synchronises `stream` twice (the flag, bounds and box; the instance boxes),
+ * and allocates nothing once the mesh's regions exist.  The builder's scratch
+ * and rocPRIM's temporary storage stay in the context until the next
+ * ctl_scene_upload or ctl_destroy.  With several ranks each rank rebuilds its
+ * own replica. */
+CTL_API ctl_status ctl_scene_rebuild_mesh(ctl_ctx* ctx, uint32_t mesh, const float* d_positions, uint32_t n_tris,
+                                          void* stream);
+/* Host wall-clock milliseconds of the last successful ctl_scene_rebuild_mesh, by
+ * its two stream synchronisations: ms[0] from the first launch until the build's
+ * flag, bounds and box are back, ms[1] from there until the instance boxes and
+ * the instance tree are done (for tools/mesh_rebuild_bench.py). */
+CTL_API ctl_status ctl_last_rebuild_ms(ctl_ctx* ctx, float ms[2]);
 
 /* ---- PrimTracer (BASELINE config C1) ------------------------------------- */
 
