@@ -29,6 +29,7 @@ import numpy as np
 from . import _abi
 from ._abi import (ImageFilter, Tonemap, LuminanceInfo, CTL_FILTER_BOX, CTL_FILTER_GAUSSIAN, CTL_FILTER_MITCHELL,
                    CTL_FILTER_LANCZOS, CTL_FILTER_TRIANGLE, CTL_FILTER_NLM, CTL_NLM_DIRECT)
+from ._abi import MaterialExt, BsdfQuery, BsdfResult
 from ._abi import (PTParams, WptParams, PrimParams, SceneDesc, Material, Pixel, Ray, Hit, CTL_SCENE_HALF_HOST_QUIRK, CTL_SCENE_BINARY_BVH,
                    CTL_BSDF_DIFFUSE, CTL_EDIFFUSE_REFLECTION, CTL_PT_MEGAKERNEL, CTL_PT_WAVEFRONT, CTL_PT_RENDER_AHEAD,
                    CTL_COMM_ID_BYTES)
@@ -38,7 +39,10 @@ __all__ = ["HostScene", "Tracer", "PathTracer", "BlockSampler", "BLOCK_INFO_DTYP
            "comm_destroy", "ImageFilter", "Tonemap", "LuminanceInfo", "image_filter", "filter_evaluate", "rgbe_encode",
            "rgbe_decode", "tonemap_constants", "CTL_FILTER_BOX", "CTL_FILTER_GAUSSIAN", "CTL_FILTER_MITCHELL",
            "CTL_FILTER_LANCZOS", "CTL_FILTER_TRIANGLE", "CTL_FILTER_NLM", "CTL_NLM_DIRECT",
-           "CTL_SCENE_HALF_HOST_QUIRK", "CTL_SCENE_BINARY_BVH", "CTL_PT_MEGAKERNEL", "CTL_PT_WAVEFRONT", "CTL_PT_RENDER_AHEAD", "lib", "diffuse_material"]
+           "CTL_SCENE_HALF_HOST_QUIRK", "CTL_SCENE_BINARY_BVH", "CTL_PT_MEGAKERNEL", "CTL_PT_WAVEFRONT", "CTL_PT_RENDER_AHEAD", "lib", "diffuse_material",
+           "MaterialExt", "BsdfQuery", "BsdfResult", "BSDF_QUERY_DTYPE", "BSDF_RESULT_DTYPE", "dielectric_material",
+           "thindielectric_material", "conductor_material", "roughconductor_material", "plastic_material",
+           "fresnel_diffuse_reflectance", "host_bsdf_eval"]
 
 
 def lib():
@@ -99,6 +103,157 @@ def roughdielectric_material(distribution, eta, alpha_u, alpha_v=None, reflectan
     m.alpha_v = float(alpha_u if alpha_v is None else alpha_v)
     m.sample_visible = 1                                         # getSampleVisible(Beckmann/GGX, true)
     return m
+
+
+def _specular_material(bsdf_type, combined, eta, reflectance, transmittance, two_sided):
+    m = Material()
+    m.alpha_texture = 0xFFFFFFFF
+    m.bsdf_type = int(bsdf_type)
+    m.combined_type = int(combined)
+    m.two_sided = 1 if two_sided else 0
+    m.node_light_index = 0xFFFFFFFF
+    m.reflectance[:] = list(reflectance)
+    m.texture = 0xFFFFFFFF
+    m.transmittance[:] = list(transmittance)
+    m.eta = float(eta)
+    m.inv_eta = float(np.float32(1.0) / np.float32(eta)) if eta else 0.0
+    return m
+
+
+def dielectric_material(eta=1.5, reflectance=(1.0, 1.0, 1.0), transmittance=(1.0, 1.0, 1.0), two_sided=False):
+    """dielectric BSDF (BSDF_Simple.cu:174-277) without dispersion: eta = DispersionCauchy B, C = 0."""
+    return _specular_material(_abi.CTL_BSDF_DIELECTRIC, _abi.CTL_EDELTA_REFLECTION | _abi.CTL_EDELTA_TRANSMISSION, eta,
+                              reflectance, transmittance, two_sided)
+
+
+def thindielectric_material(eta=1.5, reflectance=(1.0, 1.0, 1.0), transmittance=(1.0, 1.0, 1.0), two_sided=False):
+    """thindielectric BSDF (BSDF_Simple.cu:279-371)."""
+    return _specular_material(_abi.CTL_BSDF_THINDIELECTRIC, _abi.CTL_EDELTA_REFLECTION | _abi.CTL_EDELTA_TRANSMISSION,
+                              eta, reflectance, transmittance, two_sided)
+
+
+def conductor_material(eta, k, reflectance=(1.0, 1.0, 1.0), two_sided=False):
+    """conductor BSDF (BSDF_Simple.cu:617-660): (Material, MaterialExt); eta, k are rgb triples."""
+    m = _specular_material(_abi.CTL_BSDF_CONDUCTOR, _abi.CTL_EDELTA_REFLECTION, 0.0, reflectance, (0.0, 0.0, 0.0),
+                           two_sided)
+    e = MaterialExt()
+    e.eta[:] = list(eta)
+    e.k[:] = list(k)
+    return m, e
+
+
+def roughconductor_material(distribution, eta, k, alpha_u, alpha_v=None, reflectance=(1.0, 1.0, 1.0), two_sided=False):
+    """roughconductor BSDF (BSDF_Simple.cu:662-763) with constant textures: (Material, MaterialExt)."""
+    m, e = conductor_material(eta, k, reflectance, two_sided)
+    m.bsdf_type = _abi.CTL_BSDF_ROUGHCONDUCTOR
+    m.combined_type = _abi.CTL_EGLOSSY_REFLECTION
+    m.distribution = int(distribution)
+    m.alpha_u = float(alpha_u)
+    m.alpha_v = float(alpha_u if alpha_v is None else alpha_v)
+    m.sample_visible = 1                                         # getSampleVisible(Beckmann/GGX, true)
+    return m, e
+
+
+def _fresnel_dielectric_ext(cos_i, eta):
+    """FresnelHelper::fresnelDielectricExt(cosThetaI, eta) in float32 (FresnelHelper.h:27-57,191-195)."""
+    f = np.float32
+    cos_i, eta = f(cos_i), f(eta)
+    if eta == 1:
+        return f(0)
+    scale = f(1) / eta if cos_i > 0 else eta
+    t2 = f(1) - (f(1) - cos_i * cos_i) * (scale * scale)
+    if t2 <= 0:
+        return f(1)
+    ci, ct = abs(cos_i), np.sqrt(max(f(0), t2))
+    rs = (ci - eta * ct) / (ci + eta * ct)
+    rp = (eta * ci - ct) / (eta * ci + ct)
+    return f(0.5) * (rs * rs + rp * rp)
+
+
+def fresnel_diffuse_reflectance(eta):
+    """FresnelHelper::fresnelDiffuseReflectance(eta, false) (FresnelHelper.cu:13-62): the adaptive
+    Gauss-Lobatto quadrature GaussLobattoIntegrator(1024, 0, 1e-5) of Math/Integrator.h:28-153 over
+    fresnelDielectricExt(sqrt(xi), eta), xi in [0, 1], restated in float32 (sub-intervals left to right)."""
+    f = np.float32
+    eta = f(eta)
+    fn = lambda xi: _fresnel_dielectric_ext(np.sqrt(f(xi)), eta)   # noqa: E731
+    alpha, beta = np.sqrt(f(2.0) / f(3.0)), f(1.0) / np.sqrt(f(5.0))
+    x1, x2, x3 = f(0.94288241569547971906), f(0.64185334234578130578), f(0.23638319966214988028)
+    a, b = f(0), f(1)
+    max_evals, rel_error, eps, flt_max = 1024, f(1e-5), np.finfo(f).eps, np.finfo(f).max
+    m, h = (a + b) / f(2), (b - a) / f(2)
+    y1, y3, y5, y7, y9, y11, y13 = (fn(a), fn(m - alpha * h), fn(m - beta * h), fn(m), fn(m + beta * h),
+                                    fn(m + alpha * h), fn(b))
+    acc = h * (f(0.0158271919734801831) * (y1 + y13) + f(0.0942738402188500455) * (fn(m - x1 * h) + fn(m + x1 * h)) +
+               f(0.1550719873365853963) * (y3 + y11) + f(0.1888215739601824544) * (fn(m - x2 * h) + fn(m + x2 * h)) +
+               f(0.1997734052268585268) * (y5 + y9) + f(0.2249264653333395270) * (fn(m - x3 * h) + fn(m + x3 * h)) +
+               f(0.2426110719014077338) * y7)
+    evals = [13]
+    i2 = (h / f(6)) * (y1 + y13 + f(5) * (y5 + y9))
+    i1 = (h / f(1470)) * (f(77) * (y1 + y13) + f(432) * (y3 + y11) + f(625) * (y5 + y9) + f(672) * y7)
+    r = f(1)
+    if abs(i2 - acc) != 0:
+        r = abs(i1 - acc) / abs(i2 - acc)
+    if r == 0 or r > 1:
+        r = f(1)
+    tol = flt_max
+    if acc != 0:
+        tol = acc * max(rel_error, eps) / (r * eps)
+    evals[0] += 2
+
+    def step(a, b, fa, fb):
+        h, m = (b - a) / f(2), (a + b) / f(2)
+        mll, ml, mr, mrr = m - alpha * h, m - beta * h, m + beta * h, m + alpha * h
+        fmll, fml, fm, fmr, fmrr = fn(mll), fn(ml), fn(m), fn(mr), fn(mrr)
+        i2 = (h / f(6)) * (fa + fb + f(5) * (fml + fmr))
+        i1 = (h / f(1470)) * (f(77) * (fa + fb) + f(432) * (fmll + fmrr) + f(625) * (fml + fmr) + f(672) * fm)
+        evals[0] += 5
+        if evals[0] >= max_evals:
+            return i1
+        dist = tol + (i1 - i2)
+        if dist == tol or mll <= a or b <= mrr:
+            return i1
+        return (step(a, mll, fa, fmll) + step(mll, ml, fmll, fml) + step(ml, m, fml, fm) + step(m, mr, fm, fmr) +
+                step(mr, mrr, fmr, fmrr) + step(mrr, b, fmrr, fb))
+
+    with np.errstate(over="ignore"):
+        return f(f(1) * step(a, b, fn(a), fn(b)))
+
+
+def plastic_material(eta=1.5, diffuse=(0.5, 0.5, 0.5), specular=(1.0, 1.0, 1.0), nonlinear=False, texture=None,
+                     diffuse_average=None, two_sided=False):
+    """plastic BSDF (BSDF_Simple.cu:765-888): (Material, MaterialExt) with the members plastic::Update()
+    derives (BSDF_Simple.h:259-266).  `texture` = ImageTexture index of m_diffuseReflectance; pass its
+    average colour as `diffuse_average` (Texture::Average) for the specular sampling weight, which
+    otherwise uses `diffuse`."""
+    f = np.float32
+    m = _specular_material(_abi.CTL_BSDF_PLASTIC, _abi.CTL_EDELTA_REFLECTION | _abi.CTL_EDIFFUSE_REFLECTION, eta, diffuse,
+                           (0.0, 0.0, 0.0), two_sided)
+    m.texture = 0xFFFFFFFF if texture is None else int(texture)
+    e = MaterialExt()
+    e.specular[:] = list(specular)
+    e.inv_eta2 = float(f(1) / (f(eta) * f(eta)))
+    e.fdr_int = float(fresnel_diffuse_reflectance(f(1) / f(eta)))
+    lum = lambda c: f(c[0]) * f(0.212671) + f(c[1]) * f(0.715160) + f(c[2]) * f(0.072169)   # noqa: E731  Spectrum::getLuminance
+    d_avg, s_avg = lum(diffuse if diffuse_average is None else diffuse_average), lum(specular)
+    e.specular_sampling_weight = float(s_avg / (d_avg + s_avg))
+    e.nonlinear = 1 if nonlinear else 0
+    return m, e
+
+
+BSDF_QUERY_DTYPE = np.dtype([("material", "<u4"), ("op", "<u4"), ("type_mask", "<u4"), ("measure", "<u4"),
+                             ("wi", "<f4", 3), ("wo", "<f4", 3), ("sample", "<f4", 2), ("uv", "<f4", 2)])
+BSDF_RESULT_DTYPE = np.dtype([("value", "<f4", 3), ("pdf", "<f4"), ("wo", "<f4", 3), ("sampled_type", "<u4")])
+
+
+def host_bsdf_eval(desc, queries):
+    """BSDFALL::sample / f / pdf of desc's materials for an array of BSDF_QUERY_DTYPE queries, on the
+    CPU (ctl_host_bsdf_eval): BSDF_RESULT_DTYPE results, the device entry's arithmetic bit for bit."""
+    q = np.ascontiguousarray(queries, dtype=BSDF_QUERY_DTYPE)
+    out = np.zeros(q.shape[0], dtype=BSDF_RESULT_DTYPE)
+    _check(lib().ctl_host_bsdf_eval(C.byref(desc), q.shape[0], q.ctypes.data, out.ctypes.data), None,
+           "ctl_host_bsdf_eval")
+    return out
 
 
 # the reference's default parameters per filter type: (x_width, y_width, a, b)
@@ -171,8 +326,16 @@ class HostScene:
                None, "ctl_host_scene_generate")
         return self
 
-    def add_mesh(self, vertices, indices, materials, mat_index=None, normals=None, uvs=None):
+    def add_mesh(self, vertices, indices, materials, mat_index=None, normals=None, uvs=None, materials_ext=None):
+        """materials: Material records, or (Material, MaterialExt) pairs as conductor_material,
+        roughconductor_material and plastic_material return them; materials_ext: the ext records as a
+        list of its own (None entries for materials without one)."""
         import numpy as np
+        if any(isinstance(m, tuple) for m in materials):
+            if materials_ext is not None:
+                raise ValueError("add_mesh: give (Material, MaterialExt) pairs or materials_ext, not both")
+            materials_ext = [m[1] if isinstance(m, tuple) else None for m in materials]
+            materials = [m[0] if isinstance(m, tuple) else m for m in materials]
         v = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
         i = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1, 3)
         mats = (Material * len(materials))(*materials)
@@ -186,6 +349,12 @@ class HostScene:
             None if mi is None else mi.ctypes.data, mats, len(materials))
         if r < 0:
             _check(1, None, "add_mesh")
+        if materials_ext is not None and any(e is not None for e in materials_ext):
+            if len(materials_ext) != len(materials):
+                raise ValueError("add_mesh: one ext record (or None) per material")
+            ext = (MaterialExt * len(materials))(*[MaterialExt() if e is None else e for e in materials_ext])
+            _check(self._L.ctl_host_scene_set_mesh_material_ext(self._h, r, ext, len(materials)), None,
+                   "ctl_host_scene_set_mesh_material_ext")
         return r
 
     def add_texture(self, rgba, filter=_abi.CTL_TEX_TRILINEAR, wrap=_abi.CTL_WRAP_REPEAT,
@@ -640,6 +809,12 @@ class Tracer:
         wbase = self.read_array(_abi.CTL_ARRAY_MESH_WIDE_BASE, 0, wbase0.size, np.uint32, 1).reshape(-1)
         scene = self.read_array(_abi.CTL_ARRAY_SCENE_WIDE_BVH, 0, scene0.shape[0], np.float32, 32)
         return mesh, wbase, scene
+
+    def bsdf_eval(self, n, queries_ptr, results_ptr, stream=0):
+        """BSDFALL::sample / f / pdf of the uploaded scene's materials for n ctl_bsdf_query records in
+        device memory (ctl_bsdf_eval); results to n ctl_bsdf_result records in device memory."""
+        _check(self._L.ctl_bsdf_eval(self._ctx, int(n), int(queries_ptr), int(results_ptr), stream or None), self._ctx,
+               "ctl_bsdf_eval")
 
     def rays_traced(self):
         return int(self._L.ctl_rays_traced(self._ctx))

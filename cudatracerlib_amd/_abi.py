@@ -28,6 +28,11 @@ CTL_EDIFFUSE_REFLECTION = 0x2
 CTL_EGLOSSY_REFLECTION = 0x8
 CTL_EGLOSSY_TRANSMISSION = 0x10
 CTL_BSDF_ROUGHDIELECTRIC = 5
+CTL_BSDF_DIELECTRIC, CTL_BSDF_THINDIELECTRIC, CTL_BSDF_CONDUCTOR, CTL_BSDF_ROUGHCONDUCTOR, CTL_BSDF_PLASTIC = 3, 4, 6, 7, 8
+CTL_ENULL, CTL_EDELTA_REFLECTION, CTL_EDELTA_TRANSMISSION = 0x1, 0x20, 0x40
+CTL_EALL = 0x1ff
+CTL_MEASURE_SOLID_ANGLE, CTL_MEASURE_DISCRETE = 1, 4
+CTL_BSDF_OP_SAMPLE, CTL_BSDF_OP_F, CTL_BSDF_OP_PDF = 0, 1, 2
 CTL_MICROFACET_BECKMANN = 0
 CTL_MICROFACET_GGX = 1
 CTL_TEX_POINT, CTL_TEX_BILINEAR, CTL_TEX_EWA, CTL_TEX_TRILINEAR = 0, 1, 2, 3
@@ -94,6 +99,21 @@ class Material(C.Structure):        # 80 B
                 ("inv_eta", C.c_float), ("alpha_u", C.c_float), ("alpha_v", C.c_float),
                 ("sample_visible", C.c_uint32), ("alpha_state", C.c_uint32), ("alpha_texture", C.c_uint32),
                 ("alpha_threshold", C.c_float)]
+
+
+class MaterialExt(C.Structure):     # ctl_material_ext, 64 B
+    _fields_ = [("eta", C.c_float * 3), ("k", C.c_float * 3), ("specular", C.c_float * 3), ("fdr_int", C.c_float),
+                ("inv_eta2", C.c_float), ("specular_sampling_weight", C.c_float), ("nonlinear", C.c_uint32),
+                ("pad", C.c_uint32 * 3)]
+
+
+class BsdfQuery(C.Structure):       # ctl_bsdf_query, 56 B
+    _fields_ = [("material", C.c_uint32), ("op", C.c_uint32), ("type_mask", C.c_uint32), ("measure", C.c_uint32),
+                ("wi", C.c_float * 3), ("wo", C.c_float * 3), ("sample", C.c_float * 2), ("uv", C.c_float * 2)]
+
+
+class BsdfResult(C.Structure):      # ctl_bsdf_result, 32 B
+    _fields_ = [("value", C.c_float * 3), ("pdf", C.c_float), ("wo", C.c_float * 3), ("sampled_type", C.c_uint32)]
 
 
 class Texture(C.Structure):
@@ -169,6 +189,7 @@ class SceneDesc(C.Structure):
         ("anim_vertices", C.POINTER(AnimVertex)), ("n_anim_vertices", C.c_uint32),
         ("anim_triangles", C.POINTER(C.c_uint32)), ("n_anim_triangles", C.c_uint32),
         ("anim_meshes", C.POINTER(AnimMesh)), ("n_anim_meshes", C.c_uint32),
+        ("materials_ext", C.POINTER(MaterialExt)),
     ]
 
 
@@ -274,6 +295,9 @@ SYMBOLS = [
     ("ctl_host_scene_destroy", None, [_vp]),
     ("ctl_host_scene_add_mesh", C.c_int32, [_vp, _vp, C.c_uint32, _vp, C.c_uint32, _vp, _vp, _vp,
                                             C.POINTER(Material), C.c_uint32]),
+    ("ctl_host_scene_set_mesh_material_ext", C.c_int32, [_vp, C.c_uint32, C.POINTER(MaterialExt), C.c_uint32]),
+    ("ctl_host_bsdf_eval", C.c_int32, [C.POINTER(SceneDesc), C.c_uint64, _vp, _vp]),
+    ("ctl_bsdf_eval", C.c_int32, [_vp, C.c_uint64, _vp, _vp, _vp]),
     ("ctl_host_scene_add_texture", C.c_int32, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp]),
     ("ctl_host_scene_add_node", C.c_int32, [_vp, C.c_uint32, _vp]),
     ("ctl_host_scene_add_area_light", C.c_int32, [_vp, C.c_uint32, C.c_uint32, _vp]),

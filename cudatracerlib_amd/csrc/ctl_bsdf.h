@@ -1,6 +1,7 @@
 // ctl_bsdf.h — the C5 shading pieces of the PathTracer path (row a12 of
 // SURVEY.md §8): image textures with MIP-map filtering, the microfacet
-// distribution and the roughdielectric BSDF, plus the BSDF dispatch.  fp32 in
+// distribution, the roughdielectric BSDF and the five further BSDFs (dielectric,
+// thindielectric, conductor, roughconductor, plastic), plus the BSDF dispatch.  fp32 in
 // the reference's operation order (no contraction; transcendentals through
 // fp64, see ctl_math.h).
 //
@@ -10,6 +11,8 @@
 //   mf_*               MicrofacetDistribution                      Engine/MicrofacetDistribution.{h,cu}
 //   fresnel_*, reflect, refract                                    Math/FresnelHelper.h:27-160
 //   rough_*            roughdielectric::sample/f/pdf               SceneTypes/BSDF_Simple.cu:373-615
+//   mat_*              dielectric, thindielectric, conductor,      SceneTypes/BSDF_Simple.cu:174-371,
+//                      roughconductor, plastic ::sample/f/pdf                                 617-888
 //   bsdf_*             BSDFALL two-sided wrapper + dispatch        SceneTypes/BSDF.h:140-208
 #pragma once
 #include "ctl_shade.h"
@@ -702,48 +705,385 @@ CTL_HD spec diffuse_reflectance(const ctl_material& m, const dgeom& dg, const Te
     return refl(m);
 }
 
+// ---------------------------------------------------------------------------
+// dielectric, thindielectric, conductor, roughconductor, plastic
+// (BSDF_Simple.cu:174-371, 617-888), constant textures except plastic's
+// m_diffuseReflectance, no dispersion.
+//
+// FresnelHelper::fresnelConductorExact for Spectrum eta, k (FresnelHelper.h:119-142),
+// one colour channel: the Spectrum operators work per component.
+CTL_HD float fresnel_conductor_exact1(float cosThetaI, float eta, float k) {
+    const float cosThetaI2 = cosThetaI * cosThetaI, sinThetaI2 = 1 - cosThetaI2, sinThetaI4 = sinThetaI2 * sinThetaI2;
+    const float temp1 = eta * eta - k * k - sinThetaI2, a2pb2 = safe_sqrt_ref(temp1 * temp1 + k * k * eta * eta * 4),
+                a = safe_sqrt_ref((a2pb2 + temp1) * 0.5f);
+    const float term1 = a2pb2 + cosThetaI2, term2 = a * (2 * cosThetaI);
+    const float Rs2 = (term1 - term2) / (term1 + term2);
+    const float term3 = a2pb2 * cosThetaI2 + sinThetaI4, term4 = term2 * sinThetaI2;
+    const float Rp2 = Rs2 * (term3 - term4) / (term3 + term4);
+    return (Rp2 + Rs2) * 0.5f;
+}
+CTL_HD spec fresnel_conductor_exact(float cosThetaI, const ctl_material_ext& e) {
+    return mk3(fresnel_conductor_exact1(cosThetaI, e.eta[0], e.k[0]), fresnel_conductor_exact1(cosThetaI, e.eta[1], e.k[1]),
+               fresnel_conductor_exact1(cosThetaI, e.eta[2], e.k[2]));
+}
+
+#define CTL_DELTA_EPSILON 1e-3f                                                        // MathFunc.h:26
+CTL_HD f3 frame_reflect(f3 wi) { return mk3(-wi.x, -wi.y, wi.z); }                     // Frame.h:138-145
+CTL_HD f3 frame_refract(f3 wi, float cosThetaT, float eta, float invEta) {             // Frame.h:148-156
+    const float scale = -(cosThetaT < 0 ? invEta : eta);
+    return normalize(mk3(scale * wi.x, scale * wi.y, cosThetaT));
+}
+CTL_HD spec transm(const ctl_material& m) { return mk3(m.transmittance[0], m.transmittance[1], m.transmittance[2]); }
+CTL_HD spec spec_div3(spec a, spec b) { return mk3(a.x / b.x, a.y / b.y, a.z / b.z); }
+// thindielectric: R' = R + TRT + TR^3T + ..
+CTL_HD float thin_R(const ctl_material& mat, float wiz) {
+    float R = fresnel_dielectric_ext(fabsf(wiz), mat.eta);
+    const float T = 1 - R;
+    if (R < 1) R += T * T * R / (1 - R * R);
+    return R;
+}
+// plastic: m_diffuseReflectance.Evaluate(dg) (= Rd) over the internal-scattering denominator
+CTL_HD spec plastic_diff(const ctl_material_ext& e, spec Rd) {
+    if (e.nonlinear) return spec_div3(Rd, mk3s(1.0f) - Rd * e.fdr_int);
+    return spec_div(Rd, 1 - e.fdr_int);
+}
+CTL_HD float plastic_prob_specular(const ctl_material_ext& e, float Fi) {
+    return (Fi * e.specular_sampling_weight) / (Fi * e.specular_sampling_weight + (1 - Fi) * (1 - e.specular_sampling_weight));
+}
+CTL_HD Microfacet conductor_distr(const ctl_material& m) { return rough_distr(m); }
+
+// The entry points of the five types are out of line on the device, as the
+// rough dielectric's: the record's fields by value, the material and its ext
+// record as global pointers.  Rd: plastic's evaluated diffuse reflectance.
+CTL_TEX_FN RoughSample mat_sample(const ctl_material* matp, const ctl_material_ext* extp, bsdf_rec b, float pdf, f2 sample,
+                                  spec Rd) {
+    const ctl_material& mat = *matp;
+    RoughSample r;
+    r.w = mk3s(0.0f);
+    switch (mat.bsdf_type) {
+        case CTL_BSDF_DIELECTRIC: {
+            const bool sampleReflection = (b.type_mask & CTL_EDELTA_REFLECTION) != 0,
+                       sampleTransmission = (b.type_mask & CTL_EDELTA_TRANSMISSION) != 0;
+            // Dispersion::sample_eta without dispersion: f_o = 1, pdf = 1, eta = calc_eta(600), C = 0
+            const spec f_o = mk3s(1.0f);
+            const float eta_pdf = 1.0f, eta = mat.eta + 0.0f / (600.0f / 1e3f), invEta = 1.0f / eta;
+            float cosThetaT;
+            const float F = fresnel_dielectric_ext(b.wi.z, cosThetaT, eta);
+            if (sampleTransmission && sampleReflection) {
+                if (sample.x <= F) {
+                    b.sampled_type = CTL_EDELTA_REFLECTION;
+                    b.wo = frame_reflect(b.wi);
+                    pdf = F;
+                    r.w = refl(mat);
+                } else {
+                    b.sampled_type = CTL_EDELTA_TRANSMISSION;
+                    b.wo = frame_refract(b.wi, cosThetaT, eta, invEta);
+                    pdf = (1 - F) * eta_pdf;
+                    const float factor = cosThetaT < 0 ? invEta : eta;   // ERadiance
+                    r.w = f_o * transm(mat) * (factor * factor);
+                }
+            } else if (sampleReflection) {
+                b.sampled_type = CTL_EDELTA_REFLECTION;
+                b.wo = frame_reflect(b.wi);
+                pdf = 1.0f;
+                r.w = refl(mat);
+            } else if (sampleTransmission) {
+                b.sampled_type = CTL_EDELTA_TRANSMISSION;
+                b.wo = frame_refract(b.wi, cosThetaT, eta, invEta);
+                pdf = 1.0f * eta_pdf;
+                const float factor = cosThetaT < 0 ? invEta : eta;
+                r.w = f_o * transm(mat) * (factor * factor * (1 - F));
+            }
+            break;
+        }
+        case CTL_BSDF_THINDIELECTRIC: {
+            const bool sampleReflection = (b.type_mask & CTL_EDELTA_REFLECTION) != 0,
+                       sampleTransmission = (b.type_mask & CTL_ENULL) != 0;
+            const float R = thin_R(mat, b.wi.z);
+            if (sampleTransmission && sampleReflection) {
+                if (sample.x <= R) {
+                    b.sampled_type = CTL_EDELTA_REFLECTION;
+                    b.wo = frame_reflect(b.wi);
+                    pdf = R;
+                    r.w = refl(mat);
+                } else {
+                    b.sampled_type = CTL_ENULL;
+                    b.wo = -b.wi;
+                    pdf = 1 - R;
+                    r.w = transm(mat);
+                }
+            } else if (sampleReflection) {
+                b.sampled_type = CTL_EDELTA_REFLECTION;
+                b.wo = frame_reflect(b.wi);
+                pdf = 1.0f;
+                r.w = refl(mat) * R;
+            } else if (sampleTransmission) {
+                b.sampled_type = CTL_ENULL;
+                b.wo = -b.wi;
+                pdf = 1.0f;
+                r.w = transm(mat) * (1 - R);
+            }
+            break;
+        }
+        case CTL_BSDF_CONDUCTOR: {
+            const bool sampleReflection = (b.type_mask & CTL_EDELTA_REFLECTION) != 0;
+            if (!sampleReflection || b.wi.z <= 0) break;
+            b.sampled_type = CTL_EDELTA_REFLECTION;
+            b.wo = frame_reflect(b.wi);
+            pdf = 1;
+            r.w = refl(mat) * fresnel_conductor_exact(b.wi.z, *extp);
+            break;
+        }
+        case CTL_BSDF_ROUGHCONDUCTOR: {
+            if (b.wi.z < 0 || !(b.type_mask & CTL_EGLOSSY_REFLECTION)) break;
+            const Microfacet distr = conductor_distr(mat);
+            const f3 m = mf_sample(distr, b.wi, sample, pdf);
+            if (pdf == 0) break;
+            b.wo = reflect_ref(b.wi, m);
+            b.sampled_type = CTL_EGLOSSY_REFLECTION;
+            if (b.wo.z <= 0) break;
+            const spec F = fresnel_conductor_exact(dot(b.wi, m), *extp) * refl(mat);
+            float weight;
+            if (distr.sampleVisible) weight = mf_smithG1(distr, b.wo, m);
+            else weight = mf_eval(distr, m) * mf_G(distr, b.wi, b.wo, m) * dot(b.wi, m) / (pdf * b.wi.z);
+            pdf /= 4.0f * dot(b.wo, m);
+            r.w = F * weight;
+            break;
+        }
+        default: {   // CTL_BSDF_PLASTIC
+            const ctl_material_ext& e = *extp;
+            const bool hasSpecular = (b.type_mask & CTL_EDELTA_REFLECTION) != 0,
+                       hasDiffuse = (b.type_mask & CTL_EDIFFUSE_REFLECTION) != 0;
+            if ((!hasDiffuse && !hasSpecular) || b.wi.z <= 0) break;
+            const float Fi = fresnel_dielectric_ext(b.wi.z, mat.eta);
+            const spec Rs = mk3(e.specular[0], e.specular[1], e.specular[2]);
+            if (hasDiffuse && hasSpecular) {
+                const float probSpecular = plastic_prob_specular(e, Fi);
+                if (sample.x < probSpecular) {
+                    b.sampled_type = CTL_EDELTA_REFLECTION;
+                    b.wo = frame_reflect(b.wi);
+                    pdf = probSpecular;
+                    r.w = spec_div(Rs * Fi, probSpecular);
+                } else {
+                    b.sampled_type = CTL_EDIFFUSE_REFLECTION;
+                    b.wo = square_to_cosine_hemisphere(mk2((sample.x - probSpecular) / (1 - probSpecular), sample.y));
+                    const float Fo = fresnel_dielectric_ext(b.wo.z, mat.eta);
+                    const spec diff = plastic_diff(e, Rd);
+                    pdf = (1 - probSpecular) * (CTL_INV_PI * b.wo.z);
+                    r.w = diff * (e.inv_eta2 * (1 - Fi) * (1 - Fo) / (1 - probSpecular));
+                }
+            } else if (hasSpecular) {
+                b.sampled_type = CTL_EDELTA_REFLECTION;
+                b.wo = frame_reflect(b.wi);
+                pdf = 1;
+                r.w = Rs * Fi;
+            } else {
+                b.sampled_type = CTL_EDIFFUSE_REFLECTION;
+                b.wo = square_to_cosine_hemisphere(sample);
+                const float Fo = fresnel_dielectric_ext(b.wo.z, mat.eta);
+                const spec diff = plastic_diff(e, Rd);
+                pdf = CTL_INV_PI * b.wo.z;
+                r.w = diff * (e.inv_eta2 * (1 - Fi) * (1 - Fo));
+            }
+            break;
+        }
+    }
+    r.wo = b.wo; r.pdf = pdf; r.sampled_type = b.sampled_type;
+    return r;
+}
+
+CTL_TEX_FN spec mat_f(const ctl_material* matp, const ctl_material_ext* extp, bsdf_rec b, int measure, spec Rd) {
+    const ctl_material& mat = *matp;
+    const spec zero = mk3s(0.0f);
+    switch (mat.bsdf_type) {
+        case CTL_BSDF_DIELECTRIC: {
+            const bool sampleReflection = (b.type_mask & CTL_EDELTA_REFLECTION) && measure == kEDiscrete,
+                       sampleTransmission = (b.type_mask & CTL_EDELTA_TRANSMISSION) && measure == kEDiscrete;
+            const spec f_o = mk3s(1.0f);
+            const float eta = mat.eta + 0.0f / (600.0f / 1e3f), invEta = 1.0f / eta;
+            float cosThetaT;
+            const float F = fresnel_dielectric_ext(b.wi.z, cosThetaT, eta);
+            if (b.wi.z * b.wo.z >= 0) {
+                if (!sampleReflection || fabsf(dot(frame_reflect(b.wi), b.wo) - 1) > CTL_DELTA_EPSILON) return zero;
+                return refl(mat) * F;
+            }
+            if (!sampleTransmission || fabsf(dot(frame_refract(b.wi, cosThetaT, eta, invEta), b.wo) - 1) > CTL_DELTA_EPSILON)
+                return zero;
+            const float factor = cosThetaT < 0 ? invEta : eta;   // ERadiance
+            return f_o * transm(mat) * factor * factor * (1 - F);
+        }
+        case CTL_BSDF_THINDIELECTRIC: {
+            const bool sampleReflection = (b.type_mask & CTL_EDELTA_REFLECTION) && measure == kEDiscrete,
+                       sampleTransmission = (b.type_mask & CTL_ENULL) && measure == kEDiscrete;
+            const float R = thin_R(mat, b.wi.z);
+            if (b.wi.z * b.wo.z >= 0) {
+                if (!sampleReflection || fabsf(dot(frame_reflect(b.wi), b.wo) - 1) > CTL_DELTA_EPSILON) return zero;
+                return refl(mat) * R;
+            }
+            if (!sampleTransmission || fabsf(dot(-b.wi, b.wo) - 1) > CTL_DELTA_EPSILON) return zero;
+            return transm(mat) * (1 - R);
+        }
+        case CTL_BSDF_CONDUCTOR: {
+            const bool sampleReflection = (b.type_mask & CTL_EDELTA_REFLECTION) != 0;
+            if (!sampleReflection || measure != kEDiscrete || b.wi.z <= 0 || b.wo.z <= 0 ||
+                fabsf(dot(frame_reflect(b.wi), b.wo) - 1) > CTL_DELTA_EPSILON)
+                return zero;
+            return refl(mat) * fresnel_conductor_exact(b.wi.z, *extp);
+        }
+        case CTL_BSDF_ROUGHCONDUCTOR: {
+            if (measure != kESolidAngle || b.wi.z < 0 || b.wo.z < 0 || !(b.type_mask & CTL_EGLOSSY_REFLECTION)) return zero;
+            const f3 H = normalize(b.wo + b.wi);
+            const Microfacet distr = conductor_distr(mat);
+            const float D = mf_eval(distr, H);
+            if (D == 0) return zero;
+            const spec F = fresnel_conductor_exact(dot(b.wi, H), *extp) * refl(mat);
+            const float G = mf_G(distr, b.wi, b.wo, H);
+            const float value = D * G / (4.0f * b.wi.z);
+            return F * value;
+        }
+        default: {   // CTL_BSDF_PLASTIC
+            const ctl_material_ext& e = *extp;
+            const bool hasSpecular = (b.type_mask & CTL_EDELTA_REFLECTION) && measure == kEDiscrete,
+                       hasDiffuse = (b.type_mask & CTL_EDIFFUSE_REFLECTION) && measure == kESolidAngle;
+            if (b.wo.z <= 0 || b.wi.z <= 0) return zero;
+            const float Fi = fresnel_dielectric_ext(b.wi.z, mat.eta);
+            if (hasSpecular) {
+                if (fabsf(dot(frame_reflect(b.wi), b.wo) - 1) < CTL_DELTA_EPSILON)
+                    return mk3(e.specular[0], e.specular[1], e.specular[2]) * Fi;
+            } else if (hasDiffuse) {
+                const float Fo = fresnel_dielectric_ext(b.wo.z, mat.eta);
+                const spec diff = plastic_diff(e, Rd);
+                return diff * ((CTL_INV_PI * b.wo.z) * e.inv_eta2 * (1 - Fi) * (1 - Fo));
+            }
+            return zero;
+        }
+    }
+}
+
+CTL_TEX_FN float mat_pdf(const ctl_material* matp, const ctl_material_ext* extp, bsdf_rec b, int measure) {
+    const ctl_material& mat = *matp;
+    switch (mat.bsdf_type) {
+        case CTL_BSDF_DIELECTRIC: {
+            const bool sampleReflection = (b.type_mask & CTL_EDELTA_REFLECTION) && measure == kEDiscrete,
+                       sampleTransmission = (b.type_mask & CTL_EDELTA_TRANSMISSION) && measure == kEDiscrete;
+            const float eta_pdf = 1.0f, eta = mat.eta + 0.0f / (600.0f / 1e3f), invEta = 1.0f / eta;
+            float cosThetaT;
+            const float F = fresnel_dielectric_ext(b.wi.z, cosThetaT, eta);
+            if (b.wi.z * b.wo.z >= 0) {
+                if (!sampleReflection || fabsf(dot(frame_reflect(b.wi), b.wo) - 1) > CTL_DELTA_EPSILON) return 0.0f;
+                return sampleTransmission ? eta_pdf * F : 1.0f;
+            }
+            if (!sampleTransmission || fabsf(dot(frame_refract(b.wi, cosThetaT, eta, invEta), b.wo) - 1) > CTL_DELTA_EPSILON)
+                return 0.0f;
+            return sampleReflection ? 1 - F : eta_pdf * 1.0f;
+        }
+        case CTL_BSDF_THINDIELECTRIC: {
+            const bool sampleReflection = (b.type_mask & CTL_EDELTA_REFLECTION) && measure == kEDiscrete,
+                       sampleTransmission = (b.type_mask & CTL_ENULL) && measure == kEDiscrete;
+            const float R = thin_R(mat, b.wi.z);
+            if (b.wi.z * b.wo.z >= 0) {
+                if (!sampleReflection || fabsf(dot(frame_reflect(b.wi), b.wo) - 1) > CTL_DELTA_EPSILON) return 0.0f;
+                return sampleTransmission ? R : 1.0f;
+            }
+            if (!sampleTransmission || fabsf(dot(-b.wi, b.wo) - 1) > CTL_DELTA_EPSILON) return 0.0f;
+            return sampleReflection ? 1 - R : 1.0f;
+        }
+        case CTL_BSDF_CONDUCTOR: {
+            const bool sampleReflection = (b.type_mask & CTL_EDELTA_REFLECTION) != 0;
+            if (!sampleReflection || measure != kEDiscrete || b.wi.z <= 0 || b.wo.z <= 0 ||
+                fabsf(dot(frame_reflect(b.wi), b.wo) - 1) > CTL_DELTA_EPSILON)
+                return 0.0f;
+            return 1.0f;
+        }
+        case CTL_BSDF_ROUGHCONDUCTOR: {
+            if (measure != kESolidAngle || b.wi.z < 0 || b.wo.z < 0 || !(b.type_mask & CTL_EGLOSSY_REFLECTION)) return 0.0f;
+            const f3 H = normalize(b.wo + b.wi);
+            const Microfacet distr = conductor_distr(mat);
+            if (distr.sampleVisible) return mf_eval(distr, H) * mf_smithG1(distr, b.wi, H) / (4.0f * b.wi.z);
+            return mf_eval(distr, H) * H.z / (4 * absdot(b.wo, H));   // distr.pdf: pdfAll (.h:97-110)
+        }
+        default: {   // CTL_BSDF_PLASTIC
+            const ctl_material_ext& e = *extp;
+            const bool hasSpecular = (b.type_mask & CTL_EDELTA_REFLECTION) != 0,
+                       hasDiffuse = (b.type_mask & CTL_EDIFFUSE_REFLECTION) != 0;
+            if (b.wo.z <= 0 || b.wi.z <= 0) return 0.0f;
+            float probSpecular = hasSpecular ? 1.0f : 0.0f;
+            if (hasSpecular && hasDiffuse) probSpecular = plastic_prob_specular(e, fresnel_dielectric_ext(b.wi.z, mat.eta));
+            if (hasSpecular && measure == kEDiscrete) {
+                if (fabsf(dot(frame_reflect(b.wi), b.wo) - 1) < CTL_DELTA_EPSILON) return probSpecular;
+            } else if (hasDiffuse && measure == kESolidAngle) {
+                return (CTL_INV_PI * b.wo.z) * (1 - probSpecular);
+            }
+            return 0.0f;
+        }
+    }
+}
+
+CTL_HD bool bsdf_is_ext_type(uint32_t t) { return t != CTL_BSDF_DIFFUSE && t != CTL_BSDF_ROUGHDIELECTRIC; }
+
 // BSDFALL::sample/f/pdf (BSDF.h:140-208): two-sided flip of wi around the
 // lobe, then the type switch.  `tex` = the scene's texture table.  `R`: the
 // diffuse reflectance at dg when the caller already evaluated it (a textured
 // diffuse hit samples and evaluates the same texture at the same dg for the
 // BSDF sample and for next-event estimation: one lookup serves both).
 // gm: the same material in global memory (the scene's array element; required
-// for rough dielectrics), handed to the out-of-line rough-dielectric calls so
-// the caller's register copy of the 80-B record need not be written to scratch
-// for them.
+// for every type but diffuse), handed to the out-of-line calls so the caller's
+// register copy of the 80-B record need not be written to scratch for them.
+// EXT: the dispatch knows types 3, 4, 6, 7 and 8 (ge: the material's
+// ctl_material_ext record in global memory; measure: EMeasure, which only those
+// types branch on).  Without EXT the code is the two-type dispatch, which the
+// shading levels of scenes without those types keep.
+template <bool EXT = false>
 CTL_HD spec bsdf_sample(const ctl_material& m, bsdf_rec& b, float& pdf, f2 sample, const dgeom& dg, const TexView* tex,
-                        const spec* R, const ctl_material* gm) {
+                        const spec* R, const ctl_material* gm, const ctl_material_ext* ge = nullptr) {
     if (m.bsdf_type == CTL_BSDF_DIFFUSE) {
         if (!diffuse_sample_dir(m, b, pdf, sample)) return mk3s(0.0f);
         return (R ? *R : diffuse_reflectance(m, dg, tex)) * 1.0f;
     }
     const bool flip = b.wi.z < 0 && m.two_sided;
     if (flip) b.wi.z *= -1.0f;
-    const RoughSample rs = rough_sample(gm, b, pdf, sample);
+    RoughSample rs;
+    if (EXT && m.bsdf_type != CTL_BSDF_ROUGHDIELECTRIC) {
+        spec Rd = mk3s(0.0f);
+        if (m.bsdf_type == CTL_BSDF_PLASTIC) Rd = R ? *R : diffuse_reflectance(m, dg, tex);
+        rs = mat_sample(gm, ge, b, pdf, sample, Rd);
+    } else {
+        rs = rough_sample(gm, b, pdf, sample);
+    }
     b.wo = rs.wo; b.sampled_type = rs.sampled_type; pdf = rs.pdf;
     const spec res = rs.w;
     if (flip) { b.wi.z *= -1.0f; b.wo.z *= -1.0f; }
     return res;
 }
 
+template <bool EXT = false>
 CTL_HD spec bsdf_f(const ctl_material& m, bsdf_rec& b, const dgeom& dg, const TexView* tex, const spec* R,
-                   const ctl_material* gm) {
+                   const ctl_material* gm, const ctl_material_ext* ge = nullptr, int measure = kESolidAngle) {
     if (m.bsdf_type == CTL_BSDF_DIFFUSE) {
         if (!(b.type_mask & m.combined_type)) return mk3s(0.0f);
         return diffuse_f_refl(m, b, R ? *R : diffuse_reflectance(m, dg, tex));
     }
     const bool flip = b.wi.z < 0 && m.two_sided;
     if (flip) b.wi.z *= -1.0f;
-    spec res = rough_f(gm, b);
+    spec res;
+    if (EXT && m.bsdf_type != CTL_BSDF_ROUGHDIELECTRIC) {
+        spec Rd = mk3s(0.0f);
+        if (m.bsdf_type == CTL_BSDF_PLASTIC) Rd = R ? *R : diffuse_reflectance(m, dg, tex);
+        res = mat_f(gm, ge, b, measure, Rd);
+    } else {
+        res = rough_f(gm, b);
+    }
     if (flip) { b.wi.z *= -1.0f; b.wo.z *= -1.0f; }
     return res;
 }
 
-CTL_HD float bsdf_pdf(const ctl_material& m, bsdf_rec& b, const ctl_material* gm) {
+template <bool EXT = false>
+CTL_HD float bsdf_pdf(const ctl_material& m, bsdf_rec& b, const ctl_material* gm, const ctl_material_ext* ge = nullptr,
+                      int measure = kESolidAngle) {
     if (m.bsdf_type == CTL_BSDF_DIFFUSE) return diffuse_pdf(m, b);
     const bool flip = b.wi.z < 0 && m.two_sided;
     if (flip) b.wi.z *= -1.0f;
-    float res = rough_pdf(gm, b);
+    float res = EXT && m.bsdf_type != CTL_BSDF_ROUGHDIELECTRIC ? mat_pdf(gm, ge, b, measure) : rough_pdf(gm, b);
     if (flip) { b.wi.z *= -1.0f; b.wo.z *= -1.0f; }
     return res;
 }

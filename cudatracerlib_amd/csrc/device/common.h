@@ -441,9 +441,16 @@ __device__ __forceinline__ f2 primary_ray(const DevScene& S, SamplerDev& rng, ui
 // the hot kernel ~80 spilled VGPRs.  A scene with an environment map always
 // runs the env level (full shading of constant diffuse materials is exact, see
 // shade_hit).
-enum : int { kShadeLean = 0, kShadeFull = 1, kShadeEnv = 2, kShadeAlpha = 3 };
+// mat = env plus the dielectric, thindielectric, conductor, roughconductor and
+// plastic BSDFs (ctl_bsdf.h): a scene with one of those types runs this level,
+// every other scene the instantiations it ran before, whose code the five
+// types do not touch.
+enum : int { kShadeLean = 0, kShadeFull = 1, kShadeEnv = 2, kShadeAlpha = 3, kShadeMat = 4 };
 // the traversal's ALPHA flag of a shading level
-#define CTL_ALPHA_OF(F) ((F) == kShadeEnv || (F) == kShadeAlpha)
+#define CTL_ALPHA_OF(F) ((F) == kShadeEnv || (F) == kShadeAlpha || (F) == kShadeMat)
+// levels that carry the environment light, and the seven-type BSDF dispatch
+#define CTL_ENV_OF(F) ((F) == kShadeEnv || (F) == kShadeMat)
+#define CTL_EXT_OF(F) ((F) == kShadeMat)
 // kernels that never trace (wavefront shade, WPT iterate) share the full instantiation
 #define CTL_NO_TRACE_LEVEL(F) ((F) == kShadeAlpha ? kShadeFull : (F))
 
@@ -459,7 +466,7 @@ __device__ __forceinline__ float pdf_emitter(const DevScene& S, uint32_t li) {
 // environment map EvalEnvironment is 0 and the sum stays as it was.
 template <int FULL>
 __device__ __forceinline__ spec env_miss(const DevScene& S, const PathParams& P, const PathVars& v) {
-    if (FULL != kShadeEnv || S.env_index == 0xffffffffu) return (v.cf * 1.0f) * mk3s(0.0f);
+    if (!CTL_ENV_OF(FULL) || S.env_index == 0xffffffffu) return (v.cf * 1.0f) * mk3s(0.0f);
     const EnvView E = env_view(S);
     float misWeight = 1.0f;
     if (!(!P.direct || v.depth == 1 || v.specular)) {
@@ -483,7 +490,8 @@ __device__ __forceinline__ spec env_miss(const DevScene& S, const PathParams& P,
 template <int FULL>
 __device__ __forceinline__ void nee_sample(const DevScene& S, SamplerDev& rng, const ctl_material& mat,
                                            const bsdf_rec& b, const dgeom& dg, const TexView& tex, ShadowReq& sh,
-                                           const spec* R, const ctl_material* gm) {
+                                           const spec* R, const ctl_material* gm,
+                                           const ctl_material_ext* ge = nullptr) {
     f2 sample = rng.next2();
     const uint32_t nl = S.n_lights < CTL_MAX_NUM_LIGHTS ? S.n_lights : CTL_MAX_NUM_LIGHTS;
     uint32_t first = 0, cnt = nl;   // STL_upper_bound
@@ -501,18 +509,18 @@ __device__ __forceinline__ void nee_sample(const DevScene& S, SamplerDev& rng, c
     dRec.ref = dg.P; dRec.refN = dg.sys.n;
     // Light::sampleDirect dispatch: the environment map or a diffuse area light
     const f2 lsample = rng.next2();
-    spec value = FULL == kShadeEnv && S.lights[lidx].kind == CTL_LIGHT_INFINITE
+    spec value = CTL_ENV_OF(FULL) && S.lights[lidx].kind == CTL_LIGHT_INFINITE
                      ? env_sample_direct(env_view(S), dRec, lsample)
                      : light_sample_direct(S.lights[lidx], S.light_tris, S.light_tri_cdf, dRec, lsample);
     if (!spec_zero(value)) {
         bsdf_rec b2 = b;
         b2.wo = to_local(dg.sys, dRec.d);
         b2.type_mask = kEAll & ~kEDelta;
-        spec bsdfVal = FULL ? bsdf_f(mat, b2, dg, &tex, R, gm) : diffuse_f(mat, b2);
+        spec bsdfVal = FULL ? bsdf_f<CTL_EXT_OF(FULL)>(mat, b2, dg, &tex, R, gm, ge) : diffuse_f(mat, b2);
         if (!spec_zero(bsdfVal)) {
             float weight = 1.0f;
             if (dRec.measure != kEDiscrete)
-                weight = power_heuristic(dRec.pdf * lpdf, FULL ? bsdf_pdf(mat, b2, gm) : diffuse_pdf(mat, b2));
+                weight = power_heuristic(dRec.pdf * lpdf, FULL ? bsdf_pdf<CTL_EXT_OF(FULL)>(mat, b2, gm, ge) : diffuse_pdf(mat, b2));
             spec ret = value * bsdfVal * weight;
             ret = ret * mk3s(1.0f);
             sh.valid = true;
@@ -566,7 +574,9 @@ __device__ __forceinline__ bool shade_hit(const DevScene& S, const PathParams& P
     const ctl_node* N = S.nodes + node;
     fill_dg(td, load_m44(S.xf + 4 * node), mk2(r.u, r.v), P.half_quirk, LutDecode{S.normal_lut}, dg);
     b.wi = to_local(dg.sys, -v.rdir);
-    const ctl_material* gmat = S.mats + (((td.w[1] >> 16) & 0xffu) + N->material_offset);
+    const uint32_t mat_index = ((td.w[1] >> 16) & 0xffu) + N->material_offset;
+    const ctl_material* gmat = S.mats + mat_index;
+    const ctl_material_ext* gext = CTL_EXT_OF(FULL) ? S.mats_ext + mat_index : nullptr;
     const ctl_material mat = *gmat;
     if (mat.two_sided && b.wi.z < 0) {
         dg.n = -dg.n;
@@ -619,17 +629,19 @@ __device__ __forceinline__ bool shade_hit(const DevScene& S, const PathParams& P
     // when untextured, the value diffuse_reflectance returns) and handed to the
     // BSDF sample and the NEE evaluation, so the full kernel has one texture
     // call site instead of three (C5 kernel VGPR spills 27 -> 24).
-    const bool texd = FULL && mat.bsdf_type == CTL_BSDF_DIFFUSE && mat.texture != 0xffffffffu;
+    // (plastic's m_diffuseReflectance takes the same path)
+    const bool texd = FULL && (mat.bsdf_type == CTL_BSDF_DIFFUSE || (CTL_EXT_OF(FULL) && mat.bsdf_type == CTL_BSDF_PLASTIC)) &&
+                      mat.texture != 0xffffffffu;
     spec Rtex = refl(mat);
     if (texd) Rtex = diffuse_reflectance(mat, dg, &tex);
     const spec* Rp = FULL ? &Rtex : nullptr;
     if constexpr (kLazy) pk->load_sample_state(v);
     b.wo = v.wo;
-    spec f = FULL ? bsdf_sample(mat, b, v.brdf_pdf, rng.next2(), dg, &tex, Rp, gmat)
+    spec f = FULL ? bsdf_sample<CTL_EXT_OF(FULL)>(mat, b, v.brdf_pdf, rng.next2(), dg, &tex, Rp, gmat, gext)
                   : diffuse_sample(mat, b, v.brdf_pdf, rng.next2());
     v.last_nor = dg.sys.n;
     if (P.direct && (mat.combined_type & kESmooth) != 0 && S.n_lights) {   // PathTracer.cu:82-83
-        nee_sample<FULL>(S, rng, mat, b, dg, tex, sh, Rp, gmat);
+        nee_sample<FULL>(S, rng, mat, b, dg, tex, sh, Rp, gmat, gext);
     }
     if constexpr (kLazy) pk->load_cl_cf(v);
     if (sh.valid) sh.add = v.cf * sh.add;
@@ -702,7 +714,7 @@ struct MeshRegion {
 // KernelDynamicScene stream, reused by ctl_scene_update while it fits.
 enum SceneArr : int {
     SA_BVH, SA_WOOP, SA_IDX, SA_TRI, SA_MATS, SA_MESHES, SA_NODES, SA_SBVH, SA_XF, SA_IXF, SA_LIGHTS, SA_LTRIS,
-    SA_LCDF, SA_LUT, SA_TEX, SA_TEXDATA, SA_ENV, SA_ENVDATA, SA_WBVH, SA_SWBVH, SA_WBASE,
+    SA_LCDF, SA_LUT, SA_TEX, SA_TEXDATA, SA_ENV, SA_ENVDATA, SA_WBVH, SA_SWBVH, SA_WBASE, SA_MATX,
     SA_COUNT
 };
 struct SceneArray {
@@ -727,6 +739,7 @@ struct ctl_ctx {
     ctl::DevScene scene{};
     bool has_scene = false;
     bool half_quirk = false;
+    bool has_delta = false;                     // some uploaded material has a delta lobe (prim.hip)
     uint32_t nseq = 4096, len = 30;
     float* d_s1[2] = {nullptr, nullptr};
     float2* d_s2[2] = {nullptr, nullptr};

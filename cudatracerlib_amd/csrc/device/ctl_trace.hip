@@ -857,7 +857,7 @@ static ctl_status launch_schedule(ctl_ctx* c, const ctl_pt_params* p, const Path
                                dim3(kBlock), lds, s, c->scene, P, s1, s2, threads, cursor,                       \
                                c->d_counters, PS, tbl);                                                          \
         } while (0)
-#define PK2(ST, SG, WD) do { if (full == kShadeEnv) PK(ST, SG, WD, kShadeEnv); else if (full == kShadeAlpha) PK(ST, SG, WD, kShadeAlpha); \
+#define PK2(ST, SG, WD) do { if (full == kShadeMat) PK(ST, SG, WD, kShadeMat); else if (full == kShadeEnv) PK(ST, SG, WD, kShadeEnv); else if (full == kShadeAlpha) PK(ST, SG, WD, kShadeAlpha); \
                               else if (full) PK(ST, SG, WD, kShadeFull); else PK(ST, SG, WD, kShadeLean); } while (0)
         if (stats) { if (single) PK2(true, true, 0); else PK2(true, false, 0); }
         else if (wide) { if (single) PK2(false, true, 1); else PK2(false, false, 1); }
@@ -867,7 +867,7 @@ static ctl_status launch_schedule(ctl_ctx* c, const ctl_pt_params* p, const Path
     } else {
 #define MK(ST, SG, WD, FU) hipLaunchKernelGGL((path_kernel<ST, SG, WD, FU>), grid, dim3(kBlock), kStackLdsBytes, s, c->scene, \
                                               P, s1, s2, fb, c->d_counters, PS)
-#define MK2(ST, SG, WD) do { if (full == kShadeEnv) MK(ST, SG, WD, kShadeEnv); else if (full == kShadeAlpha) MK(ST, SG, WD, kShadeAlpha); \
+#define MK2(ST, SG, WD) do { if (full == kShadeMat) MK(ST, SG, WD, kShadeMat); else if (full == kShadeEnv) MK(ST, SG, WD, kShadeEnv); else if (full == kShadeAlpha) MK(ST, SG, WD, kShadeAlpha); \
                               else if (full) MK(ST, SG, WD, kShadeFull); else MK(ST, SG, WD, kShadeLean); } while (0)
         if (stats) { if (single) MK2(true, true, 0); else MK2(true, false, 0); }
         else if (wide) { if (single) MK2(false, true, 1); else MK2(false, false, 1); }
@@ -1237,7 +1237,7 @@ CTL_API ctl_status ctl_render_pass_blocks(ctl_ctx* c, const ctl_pt_params* p, co
                            dim3((unsigned)std::min<uint64_t>(nb, want)), dim3(kBlock), lds, s, c->scene, P, s1,  \
                            s2, items, cursor, c->d_counters, PS, (const uint32_t*)c->d_block_tbl);               \
     } while (0)
-#define PKL2(SG, WD) do { if (full == kShadeEnv) PKL(SG, WD, kShadeEnv); else if (full == kShadeAlpha) PKL(SG, WD, kShadeAlpha); \
+#define PKL2(SG, WD) do { if (full == kShadeMat) PKL(SG, WD, kShadeMat); else if (full == kShadeEnv) PKL(SG, WD, kShadeEnv); else if (full == kShadeAlpha) PKL(SG, WD, kShadeAlpha); \
                           else if (full) PKL(SG, WD, kShadeFull); else PKL(SG, WD, kShadeLean); } while (0)
     if (wide) { if (single) PKL2(true, 1); else PKL2(false, 1); }
     else { if (single) PKL2(true, 0); else PKL2(false, 0); }

@@ -89,7 +89,9 @@ void prim_kernel(DevScene S_arg, PathParams P_arg, PrimParams Q, const float* s1
                 b.sampled_type = 0;
                 b.type_mask = kEAll;
                 b.wi = to_local(dg.sys, -d);
-                const ctl_material* gmat = S.mats + (((td.w[1] >> 16) & 0xffu) + N->material_offset);
+                const uint32_t mat_index = ((td.w[1] >> 16) & 0xffu) + N->material_offset;
+                const ctl_material* gmat = S.mats + mat_index;
+                const ctl_material_ext* gext = CTL_EXT_OF(FULL) ? S.mats_ext + mat_index : nullptr;
                 const ctl_material mat = *gmat;
                 if (mat.two_sided && b.wi.z < 0) {
                     dg.n = -dg.n;
@@ -114,12 +116,13 @@ void prim_kernel(DevScene S_arg, PathParams P_arg, PrimParams Q, const float* s1
                 case CTL_PRIM_UV: L = mk3(dg.uv.x, dg.uv.y, 0.0f); break;
                 case CTL_PRIM_BARY_COORDS: L = mk3(h.u, h.v, 0.0f); break;
                 default: {
-                    // first_* modes; the supported BSDFs (diffuse, roughdielectric)
-                    // have no delta component, so first_non_delta_X == first_X
-                    // (PrimTracer.cu:61-67: isDelta is false)
+                    // first_* modes; without a delta component first_non_delta_X ==
+                    // first_X (PrimTracer.cu:61-67: isDelta is false).  ctl_prim_pass
+                    // refuses the first_non_delta modes for a scene with a delta
+                    // material (their bounce loop, PrimTracer.cu:68-97, is not built)
                     b.wo = mk3(0.0f, 0.0f, 1.0f);
                     const TexView tex{S.textures, S.tex_data};
-                    const spec f_avg = FULL ? bsdf_f(mat, b, dg, &tex, nullptr, gmat) : diffuse_f(mat, b);
+                    const spec f_avg = FULL ? bsdf_f<CTL_EXT_OF(FULL)>(mat, b, dg, &tex, nullptr, gmat, gext) : diffuse_f(mat, b);
                     spec Le = mk3s(0.0f);   // TraceResult::Le -> DiffuseLight::eval (Light.cu:67-82)
                     if (mat.node_light_index != 0xffffffffu) {
                         const ctl_light Lt = S.lights[N->lights[mat.node_light_index]];
@@ -135,7 +138,7 @@ void prim_kernel(DevScene S_arg, PathParams P_arg, PrimParams Q, const float* s1
                         if (S.n_lights) {
                             ShadowReq sh;
                             sh.valid = false;
-                            nee_sample<FULL>(S, rng, mat, b, dg, tex, sh, nullptr, gmat);
+                            nee_sample<FULL>(S, rng, mat, b, dg, tex, sh, nullptr, gmat, gext);
                             if (sh.valid) {
                                 // KernelDynamicScene::Occluded (KernelDynamicScene.cu:70-80)
                                 HitRec hs;
@@ -153,7 +156,7 @@ void prim_kernel(DevScene S_arg, PathParams P_arg, PrimParams Q, const float* s1
                 }
             }
         }
-        else if (FULL == kShadeEnv && S.env_index != 0xffffffffu) {
+        else if (CTL_ENV_OF(FULL) && S.env_index != 0xffffffffu) {
             // L = EvalEnvironment(r, rX, rY) (PrimTracer.cu:102): the map filtered
             // over the primary ray's differential footprint
             f3 co, dX, dY;
@@ -190,6 +193,10 @@ CTL_API ctl_status ctl_prim_pass(ctl_ctx* c, const ctl_prim_params* p, ctl_pixel
         c->err = "prim_pass: unknown draw mode";
         return CTL_ERR_INVALID;
     }
+    if (c->has_delta && p->draw_mode >= CTL_PRIM_FIRST_NON_DELTA_LE) {
+        c->err = "prim_pass: the first_non_delta modes are not supported for a scene with a delta material";
+        return CTL_ERR_INVALID;
+    }
     CTL_HIP(c, hipSetDevice(c->device));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const ctl_camera& cam = c->scene.camera;
@@ -219,7 +226,7 @@ CTL_API ctl_status ctl_prim_pass(ctl_ctx* c, const ctl_prim_params* p, ctl_pixel
                            kStackLdsBytes, s, c->scene, P, Q, c->d_s1[c->active], c->d_s2[c->active], items,     \
                            cursor, c->d_counters, d_fb, d_depth);                                                \
     } while (0)
-#define PRK2(SG, WD) do { if (full == kShadeEnv) PRK(SG, WD, kShadeEnv); else if (full == kShadeAlpha) PRK(SG, WD, kShadeAlpha); \
+#define PRK2(SG, WD) do { if (full == kShadeMat) PRK(SG, WD, kShadeMat); else if (full == kShadeEnv) PRK(SG, WD, kShadeEnv); else if (full == kShadeAlpha) PRK(SG, WD, kShadeAlpha); \
                            else if (full) PRK(SG, WD, kShadeFull); else PRK(SG, WD, kShadeLean); } while (0)
     if (wide) { if (single) PRK2(true, 1); else PRK2(false, 1); }
     else { if (single) PRK2(true, 0); else PRK2(false, 0); }

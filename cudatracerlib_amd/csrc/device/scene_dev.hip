@@ -81,6 +81,11 @@ ctl_status put(ctl_ctx* c, int a, const void* src, size_t bytes, size_t pad, hip
 template <class T>
 const T* dptr(ctl_ctx* c, int a) { return reinterpret_cast<const T*>(c->sarr[a].p); }
 
+bool bsdf_ext_type(uint32_t t) {
+    return t == CTL_BSDF_DIELECTRIC || t == CTL_BSDF_THINDIELECTRIC || t == CTL_BSDF_CONDUCTOR ||
+           t == CTL_BSDF_ROUGHCONDUCTOR || t == CTL_BSDF_PLASTIC;
+}
+
 // What ctl_scene_upload refuses (include/ctl_trace.h), per group of arrays.
 ctl_status validate(ctl_ctx* c, const ctl_scene_desc* d, uint32_t dirty) {
     if (d->n_lights > CTL_MAX_NUM_LIGHTS) { c->err = "scene_upload: more than 16 lights"; return CTL_ERR_INVALID; }
@@ -118,15 +123,51 @@ ctl_status validate(ctl_ctx* c, const ctl_scene_desc* d, uint32_t dirty) {
     if (dirty & (CTL_DIRTY_MATERIALS | CTL_DIRTY_TEXTURES)) {
         for (uint32_t i = 0; i < d->n_materials; i++) {
             const ctl_material& m = d->materials[i];
-            if (m.bsdf_type != CTL_BSDF_DIFFUSE && m.bsdf_type != CTL_BSDF_ROUGHDIELECTRIC) {
-                c->err = "scene_upload: only diffuse and roughdielectric BSDFs are supported";
+            if (m.bsdf_type != CTL_BSDF_DIFFUSE && m.bsdf_type != CTL_BSDF_ROUGHDIELECTRIC && !bsdf_ext_type(m.bsdf_type)) {
+                c->err = "scene_upload: material " + std::to_string(i) + ": BSDF type " + std::to_string(m.bsdf_type) +
+                         " is not supported (diffuse, dielectric, thindielectric, roughdielectric, conductor, "
+                         "roughconductor, plastic)";
                 return CTL_ERR_INVALID;
             }
             if (m.bsdf_type == CTL_BSDF_ROUGHDIELECTRIC && (m.distribution > CTL_MICROFACET_GGX || !m.sample_visible)) {
                 c->err = "scene_upload: roughdielectric needs a Beckmann/GGX distribution with visible-normal sampling";
                 return CTL_ERR_INVALID;
             }
-            if (m.bsdf_type == CTL_BSDF_DIFFUSE && m.texture != 0xffffffffu && m.texture >= d->n_textures) {
+            if (bsdf_ext_type(m.bsdf_type)) {
+                const std::string who = "scene_upload: material " + std::to_string(i) + ": ";
+                uint32_t lobes = 0;
+                bool need_ext = false, need_eta = false;
+                switch (m.bsdf_type) {
+                    case CTL_BSDF_DIELECTRIC:
+                    case CTL_BSDF_THINDIELECTRIC: lobes = CTL_EDELTA_REFLECTION | CTL_EDELTA_TRANSMISSION; need_eta = true; break;
+                    case CTL_BSDF_CONDUCTOR: lobes = CTL_EDELTA_REFLECTION; need_ext = true; break;
+                    case CTL_BSDF_ROUGHCONDUCTOR: lobes = CTL_EGLOSSY_REFLECTION; need_ext = true; break;
+                    default: lobes = CTL_EDELTA_REFLECTION | CTL_EDIFFUSE_REFLECTION; need_ext = need_eta = true; break;
+                }
+                // the missing array first: a description made before the ext records existed
+                // names such a type with whatever its other fields held
+                if (need_ext && !d->materials_ext) {
+                    c->err = who + "BSDF type " + std::to_string(m.bsdf_type) +
+                             " (conductor, roughconductor, plastic) needs a ctl_material_ext record; a scene without "
+                             "materials_ext holds only diffuse and roughdielectric, dielectric and thindielectric materials";
+                    return CTL_ERR_INVALID;
+                }
+                if (m.combined_type != lobes) {
+                    c->err = who + "combined_type does not match the BSDF type's lobes";
+                    return CTL_ERR_INVALID;
+                }
+                if (need_eta && !(m.eta > 0.0f)) { c->err = who + "eta must be positive"; return CTL_ERR_INVALID; }
+                if (m.bsdf_type == CTL_BSDF_ROUGHCONDUCTOR && (m.distribution > CTL_MICROFACET_GGX || !m.sample_visible)) {
+                    c->err = who + "roughconductor needs a Beckmann/GGX distribution with visible-normal sampling";
+                    return CTL_ERR_INVALID;
+                }
+                if (m.bsdf_type != CTL_BSDF_PLASTIC && m.texture != 0xffffffffu) {
+                    c->err = who + "image textures are supported for diffuse and plastic reflectance only";
+                    return CTL_ERR_INVALID;
+                }
+            }
+            if ((m.bsdf_type == CTL_BSDF_DIFFUSE || m.bsdf_type == CTL_BSDF_PLASTIC) && m.texture != 0xffffffffu &&
+                m.texture >= d->n_textures) {
                 c->err = "scene_upload: material texture index out of range";
                 return CTL_ERR_INVALID;
             }
@@ -169,6 +210,7 @@ ctl_status check_clean(ctl_ctx* c, const ctl_scene_desc* d, uint32_t dirty) {
         {CTL_DIRTY_TRI_INDICES, SA_IDX, d->n_tri_indices * sizeof(ctl_tri_index), "tri_indices"},
         {CTL_DIRTY_TRI_DATA, SA_TRI, d->n_tri_data * sizeof(ctl_triangle_data), "tri_data"},
         {CTL_DIRTY_MATERIALS, SA_MATS, d->n_materials * sizeof(ctl_material), "materials"},
+        {CTL_DIRTY_MATERIALS, SA_MATX, d->materials_ext ? d->n_materials * sizeof(ctl_material_ext) : 0, "materials_ext"},
         {CTL_DIRTY_MESHES, SA_MESHES, d->n_meshes * sizeof(ctl_kernel_mesh), "meshes"},
         {CTL_DIRTY_NODES, SA_NODES, d->n_nodes * sizeof(ctl_node), "nodes"},
         {CTL_DIRTY_NODES, SA_SBVH, (uint64_t)d->n_scene_bvh_nodes * sizeof(ctl_bvh_node), "scene_bvh_nodes"},
@@ -264,6 +306,8 @@ ctl_status commit_arrays(ctl_ctx* c, const ctl_scene_desc* d, uint32_t dirty, hi
     PUT(CTL_DIRTY_TRI_INDICES, SA_IDX, d->tri_indices, d->n_tri_indices, ctl_tri_index, 1);
     PUT(CTL_DIRTY_TRI_DATA, SA_TRI, d->tri_data, d->n_tri_data, ctl_triangle_data, 0);
     PUT(CTL_DIRTY_MATERIALS, SA_MATS, d->materials, d->n_materials, ctl_material, 0);
+    // the ext records travel with the materials (none: an empty array, never read)
+    PUT(CTL_DIRTY_MATERIALS, SA_MATX, d->materials_ext, d->materials_ext ? d->n_materials : 0, ctl_material_ext, 0);
     PUT(CTL_DIRTY_MESHES, SA_MESHES, d->meshes, d->n_meshes, ctl_kernel_mesh, 0);
     PUT(CTL_DIRTY_NODES, SA_NODES, d->nodes, d->n_nodes, ctl_node, 0);
     PUT(CTL_DIRTY_NODES, SA_SBVH, d->scene_bvh_nodes, d->n_scene_bvh_nodes, ctl_bvh_node, 0);
@@ -397,6 +441,7 @@ ctl_status commit_arrays(ctl_ctx* c, const ctl_scene_desc* d, uint32_t dirty, hi
     S.tri_idx = dptr<uint32_t>(c, SA_IDX);
     S.tri_data = dptr<ctl_triangle_data>(c, SA_TRI);
     S.mats = dptr<ctl_material>(c, SA_MATS);
+    S.mats_ext = dptr<ctl_material_ext>(c, SA_MATX);
     S.meshes = dptr<ctl_kernel_mesh>(c, SA_MESHES);
     S.nodes = dptr<ctl_node>(c, SA_NODES);
     S.scene_bvh = dptr<float4>(c, SA_SBVH);
@@ -427,6 +472,13 @@ ctl_status commit_arrays(ctl_ctx* c, const ctl_scene_desc* d, uint32_t dirty, hi
         }
         if (S.alpha) S.full_shading = kShadeAlpha;
         if (S.env_index != 0xffffffffu) S.full_shading = kShadeEnv;
+        // the five further BSDF types run their own level (common.h), so every
+        // other scene keeps the kernels it had
+        c->has_delta = false;
+        for (uint32_t i = 0; i < d->n_materials; i++) {
+            if (bsdf_ext_type(d->materials[i].bsdf_type)) S.full_shading = kShadeMat;
+            if (d->materials[i].combined_type & kEDelta) c->has_delta = true;
+        }
     }
     if (dirty & (CTL_DIRTY_NODES | CTL_DIRTY_MESHES | CTL_DIRTY_BVH)) {
         S.n_nodes = d->n_nodes;
@@ -481,6 +533,7 @@ void free_scene(ctl_ctx* c) {
     c->extra_nodes = c->extra_entries = c->extra_wide = 0;
     c->h_meshes.clear();
     c->has_scene = false;
+    c->has_delta = false;
     c->h_wbase.clear();
     c->tree_flags = 0xffffffffu;
     c->device_eps = false;

@@ -106,7 +106,7 @@ struct DevScene {
     const float4* scene_wbvh;    // instance-level wide nodes
     const uint32_t* mesh_wbase;  // first wide node of each mesh
     uint32_t wide;               // wide trees present (scene flag CTL_SCENE_BINARY_BVH clear)
-    uint32_t full_shading;       // shading level of the path kernels: kShadeLean / kShadeFull / kShadeEnv
+    uint32_t full_shading;       // shading level of the path kernels: kShadeLean .. kShadeMat
     uint32_t alpha;              // KernelDynamicScene::doAlphaMapping (some material has an alpha map)
     uint32_t s_wnode_base;
     uint32_t quant;              // wide trees in the 64-B quantized format (ctl_qnode.h)
@@ -114,6 +114,7 @@ struct DevScene {
     uint32_t env_index;
     const ctl_env_light* env;
     const float* env_data;
+    const ctl_material_ext* mats_ext;   // parallel to mats (null when the desc has none)
 };
 
 struct TraceStats {

@@ -176,7 +176,9 @@ __global__ __launch_bounds__(kBlock) void wpt_iterate_kernel(DevScene S_arg, Wpt
             dg.dudx = dg.dudy = dg.dvdx = dg.dvdy = 0.0f;
             dg.has_partials = false;   // no ray differentials in the wavefront tracer
             b.wi = to_local(dg.sys, -rd);
-            const ctl_material* gmat = S.mats + (((td.w[1] >> 16) & 0xffu) + N->material_offset);
+            const uint32_t mat_index = ((td.w[1] >> 16) & 0xffu) + N->material_offset;
+            const ctl_material* gmat = S.mats + mat_index;
+            const ctl_material_ext* gext = CTL_EXT_OF(FULL) ? S.mats_ext + mat_index : nullptr;
             const ctl_material mat = *gmat;
             if (mat.two_sided && b.wi.z < 0) {
                 dg.n = -dg.n;
@@ -206,11 +208,13 @@ __global__ __launch_bounds__(kBlock) void wpt_iterate_kernel(DevScene S_arg, Wpt
             }
             if (A.depth + 1 != A.max_path_length && surviveRR) {
                 // textured diffuse: one texture lookup for the BSDF sample and the NEE evaluation
-                const bool texd = FULL && mat.bsdf_type == CTL_BSDF_DIFFUSE && mat.texture != 0xffffffffu;
+                // (plastic's m_diffuseReflectance takes the same path)
+                const bool texd = FULL && (mat.bsdf_type == CTL_BSDF_DIFFUSE || (CTL_EXT_OF(FULL) && mat.bsdf_type == CTL_BSDF_PLASTIC)) &&
+                                  mat.texture != 0xffffffffu;
                 spec Rtex = mk3s(0.0f);
                 if (texd) Rtex = diffuse_reflectance(mat, dg, &tex);
                 const spec* Rp = texd ? &Rtex : nullptr;
-                spec f = FULL ? bsdf_sample(mat, b, bpdf, rng.next2(), dg, &tex, Rp, gmat)
+                spec f = FULL ? bsdf_sample<CTL_EXT_OF(FULL)>(mat, b, bpdf, rng.next2(), dg, &tex, Rp, gmat, gext)
                               : diffuse_sample(mat, b, bpdf, rng.next2());
                 specular = (b.sampled_type & kEDelta) != 0;
                 const f3 out = to_world(dg.sys, b.wo);
@@ -224,7 +228,7 @@ __global__ __launch_bounds__(kBlock) void wpt_iterate_kernel(DevScene S_arg, Wpt
                     float emPdf = 0.0f;
                     if (S.n_lights) {
                     const uint32_t lidx = sample_emitter(S, sample, emPdf);
-                    spec value = FULL == kShadeEnv && S.lights[lidx].kind == CTL_LIGHT_INFINITE
+                    spec value = CTL_ENV_OF(FULL) && S.lights[lidx].kind == CTL_LIGHT_INFINITE
                                      ? env_sample_direct(env_view(S), dRec, sample)
                                      : light_sample_direct(S.lights[lidx], S.light_tris, S.light_tri_cdf, dRec, sample);
                     if (dRec.pdf != 0) {
@@ -236,8 +240,8 @@ __global__ __launch_bounds__(kBlock) void wpt_iterate_kernel(DevScene S_arg, Wpt
                     if (!spec_zero(value)) {
                         b.type_mask = kEAll & ~kEDelta;
                         b.wo = to_local(dg.sys, dRec.d);
-                        spec bsdfVal = FULL ? bsdf_f(mat, b, dg, &tex, Rp, gmat) : diffuse_f(mat, b);
-                        const float bsdfPdf = FULL ? bsdf_pdf(mat, b, gmat) : diffuse_pdf(mat, b);
+                        spec bsdfVal = FULL ? bsdf_f<CTL_EXT_OF(FULL)>(mat, b, dg, &tex, Rp, gmat, gext) : diffuse_f(mat, b);
+                        const float bsdfPdf = FULL ? bsdf_pdf<CTL_EXT_OF(FULL)>(mat, b, gmat, gext) : diffuse_pdf(mat, b);
                         const float directPdf = dRec.pdf;   // measure is ESolidAngle after sampleDirect
                         const float weight = power_heuristic(directPdf, bsdfPdf);
                         const spec dF = tp * value * bsdfVal * weight;
@@ -265,7 +269,7 @@ __global__ __launch_bounds__(kBlock) void wpt_iterate_kernel(DevScene S_arg, Wpt
         } else {
             terminated = true;
             // misWeight * throughput * EvalEnvironment(ray) (WavefrontPathTracer.cu:144-157)
-            if (FULL == kShadeEnv && S.env_index != 0xffffffffu) {
+            if (CTL_ENV_OF(FULL) && S.env_index != 0xffffffffu) {
                 const EnvView E = env_view(S);
                 float misWeight = 1.0f;
                 if (NEE && !(A.depth == 0 || specular)) {
@@ -546,8 +550,8 @@ int wpt_pass(ctl_ctx* c, const ctl_wpt_params* prm, ctl_pixel* fb, hipStream_t s
 #define WPT_IT(NE, FU)                                                                                             \
     hipLaunchKernelGGL((wpt_iterate_kernel<NE, FU>), dim3(nb), dim3(kBlock), 0, s, c->scene, A, s1, s2, cnt,      \
                        B->pay[cur], B->rays[cur], B->hits, B->sec_hits, B->sec_tmp, B->flags, B->blocks, fb)
-        if (nee) { if (full == kShadeEnv) WPT_IT(true, kShadeEnv); else if (full) WPT_IT(true, kShadeFull); else WPT_IT(true, kShadeLean); }
-        else { if (full == kShadeEnv) WPT_IT(false, kShadeEnv); else if (full) WPT_IT(false, kShadeFull); else WPT_IT(false, kShadeLean); }
+        if (nee) { if (full == kShadeMat) WPT_IT(true, kShadeMat); else if (full == kShadeEnv) WPT_IT(true, kShadeEnv); else if (full) WPT_IT(true, kShadeFull); else WPT_IT(true, kShadeLean); }
+        else { if (full == kShadeMat) WPT_IT(false, kShadeMat); else if (full == kShadeEnv) WPT_IT(false, kShadeEnv); else if (full) WPT_IT(false, kShadeFull); else WPT_IT(false, kShadeLean); }
 #undef WPT_IT
         hipLaunchKernelGGL(wpt_scan_kernel, dim3(1), dim3(kScanThreads), 0, s, B->blocks, cnt, B->counts + 2 * (depth + 1));
         hipLaunchKernelGGL(wpt_scatter_kernel, dim3(nb), dim3(kBlock), 0, s, cnt, B->flags, B->blocks, B->pay[cur],

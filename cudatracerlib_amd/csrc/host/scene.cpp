@@ -87,6 +87,16 @@ void parallel_for(uint64_t n, uint32_t threads, F f) {
     for (auto& t : ts) t.join();
 }
 
+// Mesh M's materials were just appended to s->materials: keeps s->materials_ext
+// empty (no mesh so far has ext records) or parallel to s->materials, zero
+// records standing in for the meshes without any.
+void append_material_ext(ctl_host_scene* s, const ctl_host_scene::Mesh& M) {
+    if (M.materials_ext.empty() && s->materials_ext.empty()) return;
+    s->materials_ext.resize(s->materials.size() - M.materials.size(), ctl_material_ext{});
+    if (M.materials_ext.empty()) s->materials_ext.resize(s->materials.size(), ctl_material_ext{});
+    else s->materials_ext.insert(s->materials_ext.end(), M.materials_ext.begin(), M.materials_ext.end());
+}
+
 }  // namespace
 bool scene_add_light(ctl_host_scene* s, uint32_t node, uint32_t local_mat, const float L[3]) {
     uint32_t perNode = 0;
@@ -140,6 +150,17 @@ CTL_API int32_t ctl_host_scene_add_mesh(ctl_host_scene* s, const float* vertices
     m.materials.assign(materials, materials + n_materials);
     s->meshes.push_back(std::move(m));
     return (int32_t)s->meshes.size() - 1;
+}
+
+CTL_API ctl_status ctl_host_scene_set_mesh_material_ext(ctl_host_scene* s, uint32_t mesh, const ctl_material_ext* ext,
+                                                        uint32_t n) {
+    if (!s || mesh >= s->meshes.size() || !ext || n != s->meshes[mesh].materials.size()) {
+        set_host_error("set_mesh_material_ext: need a mesh and one ext record per material of it");
+        return CTL_ERR_INVALID;
+    }
+    s->meshes[mesh].materials_ext.assign(ext, ext + n);
+    s->compiled = false;
+    return CTL_OK;
 }
 
 CTL_API int32_t ctl_host_scene_add_animated_mesh(ctl_host_scene* s, const ctl_anim_vertex* vertices,
@@ -382,7 +403,7 @@ CTL_API ctl_status ctl_host_scene_compile(ctl_host_scene* s, uint32_t threads, c
     if (!s || !out) return CTL_ERR_INVALID;
     if (!s->has_camera) { set_host_error("compile: no camera"); return CTL_ERR_INVALID; }
     if (threads == 0) threads = std::max(1u, std::thread::hardware_concurrency());
-    s->tri_data.clear(); s->woop.clear(); s->bvh_nodes.clear(); s->tri_indices.clear(); s->materials.clear();
+    s->tri_data.clear(); s->woop.clear(); s->bvh_nodes.clear(); s->tri_indices.clear(); s->materials.clear(); s->materials_ext.clear();
     s->kmeshes.clear(); s->knodes.clear(); s->scene_bvh.clear(); s->xf.clear(); s->inv_xf.clear();
     s->klights.clear(); s->light_tris.clear(); s->light_tri_cdf.clear();
     s->max_mesh_depth = 0;
@@ -409,6 +430,7 @@ CTL_API ctl_status ctl_host_scene_compile(ctl_host_scene* s, uint32_t threads, c
                 m.node_light_index = 0xffffffffu;
                 s->materials.push_back(m);
             }
+            append_material_ext(s, M);
             memcpy(meshBox[mi].lo, M.c_box, 12);
             memcpy(meshBox[mi].hi, M.c_box + 3, 12);
             s->max_mesh_depth = std::max(s->max_mesh_depth, M.c_depth);
@@ -513,6 +535,7 @@ CTL_API ctl_status ctl_host_scene_compile(ctl_host_scene* s, uint32_t threads, c
             m.node_light_index = 0xffffffffu;
             s->materials.push_back(m);
         }
+        append_material_ext(s, M);
     }
     s->kmesh_box.resize(6 * s->meshes.size());
     for (size_t mi = 0; mi < s->meshes.size(); mi++) {
@@ -652,6 +675,7 @@ CTL_API ctl_status ctl_host_scene_compile(ctl_host_scene* s, uint32_t threads, c
     d.bvh_nodes = s->bvh_nodes.data(); d.n_bvh_nodes = s->bvh_nodes.size();
     d.tri_indices = s->tri_indices.data(); d.n_tri_indices = s->tri_indices.size();
     d.materials = s->materials.data(); d.n_materials = (uint32_t)s->materials.size();
+    d.materials_ext = s->materials_ext.empty() ? nullptr : s->materials_ext.data();
     d.meshes = s->kmeshes.data(); d.n_meshes = (uint32_t)s->kmeshes.size();
     d.nodes = s->knodes.data(); d.n_nodes = (uint32_t)s->knodes.size();
     d.scene_bvh_nodes = s->scene_bvh.data(); d.n_scene_bvh_nodes = (uint32_t)s->scene_bvh.size();
@@ -682,7 +706,7 @@ CTL_API ctl_status ctl_host_scene_compile(ctl_host_scene* s, uint32_t threads, c
     d.tex_data = s->tex_data.data();
     d.n_tex_data = s->tex_data.size();
     for (const ctl_material& m : s->materials)
-        if (m.bsdf_type == CTL_BSDF_DIFFUSE && m.texture != 0xffffffffu && m.texture >= s->textures.size()) {
+        if ((m.bsdf_type == CTL_BSDF_DIFFUSE || m.bsdf_type == CTL_BSDF_PLASTIC) && m.texture != 0xffffffffu && m.texture >= s->textures.size()) {
             set_host_error("compile: material texture index out of range");
             return CTL_ERR_INVALID;
         }

@@ -17,6 +17,7 @@ struct ctl_host_scene {
         std::vector<float> uv;        // per-vertex uv (may be empty)
         std::vector<uint8_t> mat;     // per triangle (may be empty)
         std::vector<ctl_material> materials;
+        std::vector<ctl_material_ext> materials_ext;   // empty, or one per material (set_mesh_material_ext)
         // compiled mesh loaded from an .xmsh file (xmsh.cpp): the arrays are
         // taken as they are, compile() only relocates them
         bool precompiled = false;
@@ -67,6 +68,7 @@ struct ctl_host_scene {
     std::vector<ctl_bvh_node> bvh_nodes;
     std::vector<ctl_tri_index> tri_indices;
     std::vector<ctl_material> materials;
+    std::vector<ctl_material_ext> materials_ext;   // empty (no mesh has ext records) or parallel to materials
     std::vector<ctl_kernel_mesh> kmeshes;
     std::vector<ctl_node> knodes;
     std::vector<ctl_bvh_node> scene_bvh;

@@ -287,6 +287,15 @@ static ctl_status write_stream(ctl_host_scene* s, uint32_t mesh, uint32_t type, 
     const uint64_t n0 = km.bvh_node_offset / 4, n1 = last ? s->bvh_nodes.size() : s->kmeshes[mesh + 1].bvh_node_offset / 4;
     const uint64_t e0 = km.bvh_indices_offset, e1 = last ? s->woop.size() : s->kmeshes[mesh + 1].bvh_indices_offset;
     const auto& M = s->meshes[mesh];
+    // the 148-byte record (Name + ctl_material) cannot carry a ctl_material_ext
+    for (uint32_t i = 0; i < M.materials.size(); i++) {
+        const uint32_t t = M.materials[i].bsdf_type;
+        if (t == CTL_BSDF_CONDUCTOR || t == CTL_BSDF_ROUGHCONDUCTOR || t == CTL_BSDF_PLASTIC) {
+            set_host_error("write_xmsh: material " + std::to_string(i) + " (conductor, roughconductor or plastic) needs a "
+                           "ctl_material_ext record, which the file's material records cannot hold");
+            return CTL_ERR_INVALID;
+        }
+    }
     std::vector<uint8_t> o;
     put(o, type);   // MeshCompileType
     put_array(o, &s->kmesh_box[6 * mesh], 6);

@@ -51,7 +51,10 @@ extern "C" {
                                ctl_animation_frame_index) and resident animations (ctl_scene_set_animation,
                                ctl_scene_animate_frame, ctl_scene_animate_time); the image pipeline
                                (ctl_image_pipeline, ctl_image_luminance, ctl_filter_evaluate, ctl_rgbe_encode /
-                               decode, ctl_tonemap_constants) */
+                               decode, ctl_tonemap_constants); BSDF types 3, 4, 6, 7, 8 (ctl_material_ext,
+                               ctl_host_scene_set_mesh_material_ext, ctl_bsdf_eval, ctl_host_bsdf_eval) and
+                               ctl_scene_desc.materials_ext appended as the desc's last member: a caller
+                               fills the desc it passes from this header (zero it first) */
 
 #if defined(_WIN32)
 #define CTL_API __declspec(dllexport)
@@ -135,16 +138,27 @@ typedef struct { float rgb[3]; float rgb_splat[3]; float weight_sum; } ctl_pixel
 
 enum {                        /* BSDF TYPE_FUNC ids (SceneTypes/BSDF_Simple.h) */
     CTL_BSDF_DIFFUSE = 1,         /* diffuse, BSDF_Simple.cu:7-75                  */
-    CTL_BSDF_ROUGHDIELECTRIC = 5  /* roughdielectric, BSDF_Simple.cu:373-615        */
+    CTL_BSDF_DIELECTRIC = 3,      /* dielectric (no dispersion), BSDF_Simple.cu:174-277 */
+    CTL_BSDF_THINDIELECTRIC = 4,  /* thindielectric, BSDF_Simple.cu:279-371         */
+    CTL_BSDF_ROUGHDIELECTRIC = 5, /* roughdielectric, BSDF_Simple.cu:373-615        */
+    CTL_BSDF_CONDUCTOR = 6,       /* conductor, BSDF_Simple.cu:617-660              */
+    CTL_BSDF_ROUGHCONDUCTOR = 7,  /* roughconductor, BSDF_Simple.cu:662-763         */
+    CTL_BSDF_PLASTIC = 8          /* plastic, BSDF_Simple.cu:765-888                */
 };
 
 /* EBSDFType bits used by the path (SceneTypes/Samples.h:32-60). */
 enum {
+    CTL_ENULL = 0x00001,
     CTL_EDIFFUSE_REFLECTION = 0x00002,
     CTL_EDIFFUSE_TRANSMISSION = 0x00004,
     CTL_EGLOSSY_REFLECTION = 0x00008,
-    CTL_EGLOSSY_TRANSMISSION = 0x00010
+    CTL_EGLOSSY_TRANSMISSION = 0x00010,
+    CTL_EDELTA_REFLECTION = 0x00020,
+    CTL_EDELTA_TRANSMISSION = 0x00040
 };
+
+/* EMeasure values the BSDFs branch on (SceneTypes/Samples.h). */
+enum { CTL_MEASURE_SOLID_ANGLE = 1, CTL_MEASURE_DISCRETE = 4 };
 
 /* MicrofacetDistribution::EType (Engine/MicrofacetDistribution.h:14-21). */
 enum { CTL_MICROFACET_BECKMANN = 0, CTL_MICROFACET_GGX = 1 };
@@ -173,6 +187,54 @@ typedef struct {
     uint32_t alpha_texture;      /* ImageTexture of AlphaMap.tex (states 1, 2)    */
     float alpha_threshold;       /* AlphaMap.test_val_scalar                     */
 } ctl_material;
+
+/* Field use of the other BSDFs (constant textures; no dispersion):
+ *   dielectric       reflectance = m_specularReflectance, transmittance =
+ *                    m_specularTransmittance, eta = Dispersion B (C = 0);
+ *                    combined_type EDeltaReflection | EDeltaTransmission
+ *   thindielectric   as dielectric, eta = m_eta; combined_type the same (its
+ *                    transmitted lobe tests and reports ENull, as the reference)
+ *   conductor        reflectance = m_specularReflectance; ext.eta / ext.k;
+ *                    combined_type EDeltaReflection
+ *   roughconductor   conductor + distribution, alpha_u, alpha_v, sample_visible;
+ *                    combined_type EGlossyReflection
+ *   plastic          reflectance / texture = m_diffuseReflectance (image texture
+ *                    allowed as for diffuse), eta = m_eta; ext.specular, fdr_int,
+ *                    inv_eta2, specular_sampling_weight, nonlinear as
+ *                    plastic::Update() computes them; combined_type
+ *                    EDeltaReflection | EDiffuseReflection
+ * The parameters that do not fit the 80-B record travel in a parallel array of
+ * ctl_material_ext records (ctl_scene_desc.materials_ext), 64 B each; types 6,
+ * 7 and 8 need it. */
+typedef struct {
+    float eta[3], k[3];               /* conductor, roughconductor: m_eta, m_k      */
+    float specular[3];                /* plastic: m_specularReflectance             */
+    float fdr_int;                    /* plastic: m_fdrInt                          */
+    float inv_eta2;                   /* plastic: m_invEta2                         */
+    float specular_sampling_weight;   /* plastic: m_specularSamplingWeight          */
+    uint32_t nonlinear;               /* plastic: m_nonlinear                       */
+    uint32_t pad[3];
+} ctl_material_ext;
+
+/* One query of ctl_bsdf_eval / ctl_host_bsdf_eval: BSDFALL::sample, f or pdf of
+ * material `material` of the scene, through the dispatch the integrators use.
+ * Directions are in the local shading frame; uv has no partials. */
+enum { CTL_BSDF_OP_SAMPLE = 0, CTL_BSDF_OP_F = 1, CTL_BSDF_OP_PDF = 2 };
+typedef struct {
+    uint32_t material;     /* index into materials[]                         */
+    uint32_t op;           /* CTL_BSDF_OP_*                                   */
+    uint32_t type_mask;    /* BSDFSamplingRecord::typeMask                    */
+    uint32_t measure;      /* CTL_MEASURE_* (f and pdf)                       */
+    float wi[3], wo[3];    /* wo: read by f and pdf                           */
+    float sample[2];       /* sample                                          */
+    float uv[2];
+} ctl_bsdf_query;          /* 56 B */
+typedef struct {
+    float value[3];        /* sample: the weight; f: the value; pdf: 0        */
+    float pdf;             /* sample, pdf                                     */
+    float wo[3];           /* the record's wo after the call                  */
+    uint32_t sampled_type; /* the record's sampledType after the call         */
+} ctl_bsdf_result;         /* 32 B */
 
 /* ImageTexture (SceneTypes/Texture.h:159-183) with its TextureMapping2D and
  * the KernelMIPMap it samples (Engine/MIPMap_device.h:59-80).  Texels are
@@ -339,6 +401,8 @@ typedef struct {
     const ctl_anim_vertex* anim_vertices; uint32_t n_anim_vertices;
     const uint32_t* anim_triangles;     uint32_t n_anim_triangles;   /* 3 indices each */
     const ctl_anim_mesh* anim_meshes;   uint32_t n_anim_meshes;
+    /* NULL, or n_materials records parallel to materials[] (BSDF types 6-8) */
+    const ctl_material_ext* materials_ext;
 } ctl_scene_desc;
 
 /* PathTracer parameters (Integrators/PathTracer.h:10-19) + multi-GPU tiling. */
@@ -1129,6 +1193,18 @@ CTL_API ctl_status ctl_host_scene_compile(ctl_host_scene* s, uint32_t threads, c
  * ctl_scene_animate.  uvs: 2 floats per vertex or NULL; mat_index as
  * ctl_host_scene_add_mesh.  Area lights on animated meshes are refused at
  * compile (their ShapeSet would go stale).  Returns the mesh index or -1. */
+/* Attaches ctl_material_ext records to mesh `mesh`'s materials (n = the mesh's
+ * material count); ctl_host_scene_compile lays them out parallel to materials. */
+CTL_API ctl_status ctl_host_scene_set_mesh_material_ext(ctl_host_scene* s, uint32_t mesh, const ctl_material_ext* ext,
+                                                        uint32_t n);
+/* BSDFALL::sample / f / pdf for n queries against desc's materials, on the CPU
+ * (no GPU needed): the arithmetic of ctl_bsdf_eval bit for bit. */
+CTL_API ctl_status ctl_host_bsdf_eval(const ctl_scene_desc* desc, uint64_t n, const ctl_bsdf_query* queries,
+                                      ctl_bsdf_result* results);
+/* The same for the uploaded scene's materials, on the device: d_queries and
+ * d_results are device arrays of n records. */
+CTL_API ctl_status ctl_bsdf_eval(ctl_ctx* ctx, uint64_t n, const ctl_bsdf_query* d_queries,
+                                 ctl_bsdf_result* d_results, void* stream);
 CTL_API int32_t ctl_host_scene_add_animated_mesh(ctl_host_scene* s, const ctl_anim_vertex* vertices,
                                                  uint32_t n_vertices, const uint32_t* indices, uint32_t n_triangles,
                                                  const float* uvs, const uint8_t* mat_index,
