@@ -17,6 +17,16 @@ TIE_FIRST_FOUND = 0   # the reference's binary visit order (the reference semant
 TRAVERSE_WIDE = 2     # the product's 4-wide per-ray order over trees registered with oracle_set_wide
 # any-hit shadow query culling: tmax - eps (round 4) / tmax / none / tmax + slab slack (the product's)
 CULL_AT_ACCEPT, CULL_AT_TMAX, CULL_AT_INF, CULL_SLAB = 0, 1, 2, 3
+# oracle_render_pass_events: what each of the seven counters counts over a pass
+EVENTS = ("delta_bounce", "tir", "emitter_after_specular", "env_after_specular", "nee_on_delta_and_smooth",
+          "ended_by_length", "rr_draw")
+# the entries that shade: they refuse a scene with a material the oracle does not restate
+SHADING_ENTRIES = ("oracle_render_pass", "oracle_render_pass_events", "oracle_prim_pass", "oracle_wpt_render_pass",
+                   "oracle_bsdf_eval")
+
+
+class OracleError(RuntimeError):
+    """An oracle entry refused its input (oracle_last_error)."""
 
 
 def build():
@@ -66,14 +76,49 @@ def load():
         "oracle_env_tables": (None, [vp, vp, vp, vp]),
         "oracle_env_sample": (None, [C.POINTER(SceneDesc), C.c_uint64, vp, vp]),
         "oracle_env_eval": (None, [C.POINTER(SceneDesc), C.c_uint64, vp, vp]),
+        "oracle_render_pass_events": (C.c_uint64, [C.POINTER(SceneDesc), C.POINTER(PTParams), C.c_uint64, vp, C.c_int32,
+                                                   C.c_int32, vp]),
+        "oracle_bsdf_eval": (C.c_int32, [C.POINTER(SceneDesc), C.c_uint64, vp, vp]),
+        "oracle_last_error": (C.c_char_p, []),
+        "oracle_clear_error": (None, []),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
         f.restype = res
         f.argtypes = args
+
+    def refused(result, func, args):
+        failed = result == 0xFFFFFFFFFFFFFFFF if func.restype is C.c_uint64 else result != 0
+        if failed:
+            msg = L.oracle_last_error().decode()
+            L.oracle_clear_error()
+            raise OracleError(msg or func.__name__ + " failed")
+        return result
+
+    for name in SHADING_ENTRIES:
+        getattr(L, name).errcheck = refused
     _lib = L
     return L
 
 
 def ptr(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+def bsdf_eval(desc, queries):
+    """BSDFALL::sample / f / pdf for an array of BSDF_QUERY_DTYPE records (oracle_bsdf_eval):
+    BSDF_RESULT_DTYPE results, laid out and answered as cudatracerlib_amd.host_bsdf_eval's."""
+    import numpy as np
+    from cudatracerlib_amd import BSDF_QUERY_DTYPE, BSDF_RESULT_DTYPE
+    q = np.ascontiguousarray(queries, dtype=BSDF_QUERY_DTYPE)
+    out = np.zeros(q.shape[0], dtype=BSDF_RESULT_DTYPE)
+    load().oracle_bsdf_eval(C.byref(desc), q.shape[0], q.ctypes.data, out.ctypes.data)
+    return out
+
+
+def render_pass_events(desc, params, pass_index, fb, tie, threads=0):
+    """One oracle_render_pass into fb; -> (rays, {event name: count}) of that pass."""
+    import numpy as np
+    ev = np.zeros(len(EVENTS), np.uint64)
+    rays = load().oracle_render_pass_events(C.byref(desc), C.byref(params), pass_index, ptr(fb), tie, threads, ptr(ev))
+    return rays, dict(zip(EVENTS, (int(x) for x in ev)))

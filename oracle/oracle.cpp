@@ -33,6 +33,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <string>
 
 using namespace oracle;
 
@@ -799,29 +800,105 @@ float diffuse_pdf(const ctl_material& m, BRec& b) {
     return res;
 }
 
-// BSDFALL::sample / f / pdf (BSDF.h:140-208): the type switch; diffuse does its
-// own two-sided flip above, roughdielectric gets the wrapper here.
-Spec bsdf_sample(const ctl_scene_desc* d, const ctl_material& m, BRec& b, float& pdf, V2 sample) {
+}  // namespace
+#include "oracle_mat.h"
+namespace {
+
+// What the dispatch below restates.  Anything else is refused by every entry
+// that shades (shading_refusal), never shaded as some other type.
+bool material_restated(const ctl_scene_desc* d, uint32_t i, std::string& why) {
+    const ctl_material& m = d->materials[i];
+    const uint32_t t = m.bsdf_type;
+    const std::string who = "material " + std::to_string(i) + " (bsdf_type " + std::to_string(t) + ")";
+    if (t != CTL_BSDF_DIFFUSE && (t < CTL_BSDF_DIELECTRIC || t > CTL_BSDF_PLASTIC)) {
+        why = who + ": BSDF type not restated by the oracle";
+        return false;
+    }
+    if ((t == CTL_BSDF_CONDUCTOR || t == CTL_BSDF_ROUGHCONDUCTOR || t == CTL_BSDF_PLASTIC) && !d->materials_ext) {
+        why = who + " needs a ctl_material_ext record (materials_ext is null)";
+        return false;
+    }
+    if ((t == CTL_BSDF_ROUGHDIELECTRIC || t == CTL_BSDF_ROUGHCONDUCTOR) &&
+        (m.distribution > CTL_MICROFACET_GGX || !m.sample_visible)) {
+        why = who + ": only Beckmann/GGX with visible-normal sampling is restated";
+        return false;
+    }
+    return true;
+}
+std::mutex g_err_mtx;
+std::string g_err;
+void set_error(const std::string& s) { std::lock_guard<std::mutex> g(g_err_mtx); g_err = s; }
+// true (and the message kept for oracle_last_error) if the scene holds a material the oracle cannot shade
+bool shading_refusal(const ctl_scene_desc* d, const char* entry) {
+    std::string why;
+    for (uint32_t i = 0; i < d->n_materials; i++)
+        if (!material_restated(d, i, why)) { set_error(std::string(entry) + ": " + why); return true; }
+    return false;
+}
+
+// BSDFALL::sample / f / pdf (BSDF.h:140-208): the type switch under the
+// two-sided wrapper (start_two_sided<true, false> flips wi, end_two_sided<true,
+// true> flips wi and wo back); diffuse does its own flip above.  A type that is
+// not restated never gets here (shading_refusal); reaching the end is a bug.
+const ctl_material_ext& ext_of(const ctl_scene_desc* d, const ctl_material& m) { return d->materials_ext[&m - d->materials]; }
+[[noreturn]] void unreachable_type(const ctl_material& m) {
+    std::fprintf(stderr, "oracle: BSDF type %u reached the dispatch\n", m.bsdf_type);
+    std::abort();
+}
+Spec bsdf_sample(const ctl_scene_desc* d, const ctl_material& m, BRec& b, float& pdf, V2 sample, uint64_t* tir = nullptr) {
     if (m.bsdf_type == CTL_BSDF_DIFFUSE) return diffuse_sample(d, m, b, pdf, sample);
     bool flip = b.wi.z < 0 && m.two_sided;
     if (flip) b.wi.z *= -1.0f;
-    Spec r = c5::rough_sample(m, b, pdf, sample);
+    Spec r;
+    switch (m.bsdf_type) {
+        case CTL_BSDF_DIELECTRIC: r = omat::dielectric_sample(m, b, pdf, sample, tir); break;
+        case CTL_BSDF_THINDIELECTRIC: r = omat::thin_sample(m, b, pdf, sample); break;
+        case CTL_BSDF_ROUGHDIELECTRIC: r = c5::rough_sample(m, b, pdf, sample); break;
+        case CTL_BSDF_CONDUCTOR: r = omat::conductor_sample(m, ext_of(d, m), b, pdf, sample); break;
+        case CTL_BSDF_ROUGHCONDUCTOR: r = omat::roughconductor_sample(m, ext_of(d, m), b, pdf, sample); break;
+        case CTL_BSDF_PLASTIC: r = omat::plastic_sample(d, m, ext_of(d, m), b, pdf, sample); break;
+        default: unreachable_type(m);
+    }
     if (flip) { b.wi.z *= -1.0f; b.wo.z *= -1.0f; }
     return r;
 }
-Spec bsdf_f(const ctl_scene_desc* d, const ctl_material& m, BRec& b) {
-    if (m.bsdf_type == CTL_BSDF_DIFFUSE) return diffuse_f(d, m, b);
+Spec bsdf_f(const ctl_scene_desc* d, const ctl_material& m, BRec& b, int measure = omat::MSolidAngle) {
+    if (m.bsdf_type == CTL_BSDF_DIFFUSE) {   // diffuse::f: measure != ESolidAngle -> 0 (BSDF_Simple.cu:39)
+        if (measure != omat::MSolidAngle) { BRec t = b; t.typeMask = 0; Spec r = diffuse_f(d, m, t); b.wo = t.wo; return r; }
+        return diffuse_f(d, m, b);
+    }
     bool flip = b.wi.z < 0 && m.two_sided;
     if (flip) b.wi.z *= -1.0f;
-    Spec r = c5::rough_f(m, b);
+    Spec r;
+    switch (m.bsdf_type) {
+        case CTL_BSDF_DIELECTRIC: r = omat::dielectric_f(m, b, measure); break;
+        case CTL_BSDF_THINDIELECTRIC: r = omat::thin_f(m, b, measure); break;
+        case CTL_BSDF_ROUGHDIELECTRIC: r = measure != omat::MSolidAngle ? v3s(0.0f) : c5::rough_f(m, b); break;   // :439
+        case CTL_BSDF_CONDUCTOR: r = omat::conductor_f(m, ext_of(d, m), b, measure); break;
+        case CTL_BSDF_ROUGHCONDUCTOR: r = omat::roughconductor_f(m, ext_of(d, m), b, measure); break;
+        case CTL_BSDF_PLASTIC: r = omat::plastic_f(d, m, ext_of(d, m), b, measure); break;
+        default: unreachable_type(m);
+    }
     if (flip) { b.wi.z *= -1.0f; b.wo.z *= -1.0f; }
     return r;
 }
-float bsdf_pdf(const ctl_scene_desc*, const ctl_material& m, BRec& b) {
-    if (m.bsdf_type == CTL_BSDF_DIFFUSE) return diffuse_pdf(m, b);
+float bsdf_pdf(const ctl_scene_desc* d, const ctl_material& m, BRec& b, int measure = omat::MSolidAngle) {
+    if (m.bsdf_type == CTL_BSDF_DIFFUSE) {   // diffuse::pdf: measure != ESolidAngle -> 0 (BSDF_Simple.cu:59)
+        if (measure != omat::MSolidAngle) { BRec t = b; t.typeMask = 0; float r = diffuse_pdf(m, t); b.wo = t.wo; return r; }
+        return diffuse_pdf(m, b);
+    }
     bool flip = b.wi.z < 0 && m.two_sided;
     if (flip) b.wi.z *= -1.0f;
-    float r = c5::rough_pdf(m, b);
+    float r;
+    switch (m.bsdf_type) {
+        case CTL_BSDF_DIELECTRIC: r = omat::dielectric_pdf(m, b, measure); break;
+        case CTL_BSDF_THINDIELECTRIC: r = omat::thin_pdf(m, b, measure); break;
+        case CTL_BSDF_ROUGHDIELECTRIC: r = measure != omat::MSolidAngle ? 0.0f : c5::rough_pdf(m, b); break;   // :375
+        case CTL_BSDF_CONDUCTOR: r = omat::conductor_pdf(b, measure); break;
+        case CTL_BSDF_ROUGHCONDUCTOR: r = omat::roughconductor_pdf(m, b, measure); break;
+        case CTL_BSDF_PLASTIC: r = omat::plastic_pdf(m, ext_of(d, m), b, measure); break;
+        default: unreachable_type(m);
+    }
     if (flip) { b.wi.z *= -1.0f; b.wo.z *= -1.0f; }
     return r;
 }
@@ -1021,7 +1098,12 @@ struct RenderCtx {
     bool anyHitShadow;
     uint64_t rays = 0;
     Stats st;
+    uint64_t* ev = nullptr;   // oracle_render_pass_events: EV_* counters of this worker
 };
+// Branches a pass went through (oracle_render_pass_events), so a test can show
+// that its scene reaches them.
+enum { EV_DELTA_BOUNCE = 0, EV_TIR, EV_EMITTER_AFTER_SPECULAR, EV_ENV_AFTER_SPECULAR, EV_NEE_ON_DELTA_AND_SMOOTH,
+       EV_ENDED_BY_LENGTH, EV_RR_DRAW, EV_COUNT };
 
 // KernelDynamicScene::Occluded(Ray(ori, dir), 0, tmax) (KernelDynamicScene.cu:70-80).
 // Closest-hit form (the reference): traceRay, then eps < t < tmax - eps; a miss
@@ -1113,6 +1195,9 @@ Spec path_trace(RenderCtx& C, V3 rori, V3 rdir, V3 rXo, V3 rXd, V3 rYo, V3 rYd, 
     float brdf_scattering_pdf = 0;
     V3 last_nor = v3(0, 0, 0);
     Hit r2;
+    uint64_t none[EV_COUNT] = {};
+    uint64_t* ev = C.ev ? C.ev : none;
+    bool rrEnded = false;
     while (depth++ < maxPathLength) {
         C.rays++;
         trace_ray(C.S, rori, rdir, r2, C.tie, &C.st);
@@ -1134,6 +1219,7 @@ Spec path_trace(RenderCtx& C, V3 rori, V3 rdir, V3 rXo, V3 rXd, V3 rYo, V3 rYd, 
             if (li != UINT_MAX) {
                 float misWeight = 1.0f;
                 const ctl_light& L = d->lights[li];
+                if (depth > 1 && specularBounce) ev[EV_EMITTER_AFTER_SPECULAR]++;
                 if (!(!direct || depth == 1 || specularBounce)) {
                     DRec dRec;   // DirectSamplingRecFromRay (TraceAlgorithms.cu:33-42)
                     dRec.ref = rori; dRec.refN = last_nor; dRec.p = bRec.dg.P; dRec.n = bRec.dg.n;
@@ -1146,22 +1232,29 @@ Spec path_trace(RenderCtx& C, V3 rori, V3 rdir, V3 rXo, V3 rXd, V3 rYo, V3 rYd, 
                 Spec Le = (dot(bRec.dg.sys.n, w) <= 0) ? v3s(0.0f) : v3(L.radiance[0], L.radiance[1], L.radiance[2]);
                 cl = cl + (cf * misWeight) * Le;
             }
-            Spec f = bsdf_sample(d, mat, bRec, brdf_scattering_pdf, C.rng->randomFloat2());
+            Spec f = bsdf_sample(d, mat, bRec, brdf_scattering_pdf, C.rng->randomFloat2(), &ev[EV_TIR]);
             last_nor = bRec.dg.sys.n;
-            if (direct && (mat.combined_type & ESmooth) != 0) cl = cl + cf * uniform_sample_one_light(C, bRec, mat);
+            if (direct && (mat.combined_type & ESmooth) != 0) {
+                if (mat.combined_type & EDelta) ev[EV_NEE_ON_DELTA_AND_SMOOTH]++;
+                cl = cl + cf * uniform_sample_one_light(C, bRec, mat);
+            }
             specularBounce = (bRec.sampledType & EDelta) != 0;
+            if (specularBounce) ev[EV_DELTA_BOUNCE]++;
             cf = cf * f;
             rori = bRec.dg.P;
             rdir = toWorld(bRec.dg.sys, bRec.wo);
         }
         if (r2.tri == UINT_MAX) break;
         if (depth > rrStartDepth && !specularBounce) {
-            if (C.rng->randomFloat() >= spec_max(cf)) break;
+            ev[EV_RR_DRAW]++;
+            if (C.rng->randomFloat() >= spec_max(cf)) { rrEnded = true; break; }
             cf = spec_div(cf, spec_max(cf));
         }
     }
+    if (r2.tri != UINT_MAX && !rrEnded) ev[EV_ENDED_BY_LENGTH]++;
     if (r2.tri == UINT_MAX) {   // PathTracer.cu:98-111
         float misWeight = 1.0f;
+        if (depth > 1 && specularBounce) ev[EV_ENV_AFTER_SPECULAR]++;
         if (!(!direct || depth == 1 || specularBounce) && d->env_map_index != UINT_MAX) {
             DRec dRec;   // DirectSamplingRecFromRay(r, dist, last_nor, 0, 0): solid angle along r
             dRec.ref = rori; dRec.refN = last_nor; dRec.d = rdir; dRec.dist = r2.t; dRec.measure = ESolidAngle;
@@ -1977,8 +2070,12 @@ void oracle_brute_force(const ctl_scene_desc* d, int64_t n, const ctl_ray* rays,
 // lands on one of its pixels (the product's apron items), and drops its own
 // samples that land on another rank's pixel, so the ranks' framebuffers sum to
 // the 1-rank framebuffer bit for bit.
-uint64_t oracle_render_pass(const ctl_scene_desc* desc, const ctl_pt_params* prm, uint64_t pass_index,
-                            ctl_pixel* fb, int32_t tie, int32_t threads, uint32_t pixel_stride, uint64_t* stats) {
+// A scene with a material the oracle does not restate is refused: nothing is
+// rendered, UINT64_MAX is returned and oracle_last_error() says why.  events,
+// if given, gets the pass's EV_* counts added (EV_COUNT values).
+static uint64_t render_pass(const ctl_scene_desc* desc, const ctl_pt_params* prm, uint64_t pass_index, ctl_pixel* fb,
+                            int32_t tie, int32_t threads, uint32_t pixel_stride, uint64_t* stats, uint64_t* events) {
+    if (shading_refusal(desc, "oracle_render_pass")) return UINT64_MAX;
     const uint32_t nseq = 4096, len = 30;
     std::vector<float> s1((size_t)nseq * len), s2((size_t)nseq * len * 2);
     sampler_tables(pass_index, nseq, len, s1.data(), s2.data());
@@ -2004,6 +2101,8 @@ uint64_t oracle_render_pass(const ctl_scene_desc* desc, const ctl_pt_params* prm
     auto worker = [&]() {
         RenderCtx C{SceneView{desc}, nullptr, tie, (desc->flags & CTL_SCENE_HALF_HOST_QUIRK) != 0,
                     prm->shadow_any_hit != 0};
+        uint64_t ev[EV_COUNT] = {};
+        if (events) C.ev = ev;
         for (;;) {
             int64_t y = nextRow.fetch_add(1);
             if (y >= (int64_t)H) break;
@@ -2027,6 +2126,7 @@ uint64_t oracle_render_pass(const ctl_scene_desc* desc, const ctl_pt_params* prm
         std::lock_guard<std::mutex> g(mtx);
         totalRays += C.rays;
         acc[0] += C.st.nodes; acc[1] += C.st.tris; acc[2] += C.st.inst;
+        if (events) for (int k = 0; k < EV_COUNT; k++) events[k] += ev[k];
     };
     std::vector<std::thread> tv;
     for (int i = 0; i < threads; i++) tv.emplace_back(worker);
@@ -2036,11 +2136,73 @@ uint64_t oracle_render_pass(const ctl_scene_desc* desc, const ctl_pt_params* prm
     if (stats) { stats[0] = totalRays; stats[1] = acc[0]; stats[2] = acc[1]; stats[3] = acc[2]; }
     return totalRays;
 }
+uint64_t oracle_render_pass(const ctl_scene_desc* desc, const ctl_pt_params* prm, uint64_t pass_index,
+                            ctl_pixel* fb, int32_t tie, int32_t threads, uint32_t pixel_stride, uint64_t* stats) {
+    return render_pass(desc, prm, pass_index, fb, tie, threads, pixel_stride, stats, nullptr);
+}
+// oracle_render_pass that also adds the pass's event counts to events[7]: delta
+// bounces, total internal reflections, emitter hits after a specular bounce,
+// environment escapes after a specular bounce, NEE evaluations on a material
+// with delta and smooth lobes, paths ended by max_path_length, RR draws.
+uint64_t oracle_render_pass_events(const ctl_scene_desc* desc, const ctl_pt_params* prm, uint64_t pass_index,
+                                   ctl_pixel* fb, int32_t tie, int32_t threads, uint64_t* events) {
+    return render_pass(desc, prm, pass_index, fb, tie, threads, 1, nullptr, events);
+}
+
+// The message of the last refusal ("" if none) and its reset.  The Python
+// binding raises it after every entry that shades.
+const char* oracle_last_error() {
+    static thread_local std::string copy;
+    std::lock_guard<std::mutex> g(g_err_mtx);
+    copy = g_err;
+    return copy.c_str();
+}
+void oracle_clear_error() { set_error(""); }
+
+// BSDFALL::sample / f / pdf for an array of ctl_bsdf_query records, answered as
+// ctl_host_bsdf_eval answers them: the shading frame is the identity, the
+// record's uv has no partials, a query naming a material the scene does not
+// have gets a zero value and sampled_type all ones.  Returns 0, or -1 refused.
+int32_t oracle_bsdf_eval(const ctl_scene_desc* d, uint64_t n, const ctl_bsdf_query* queries, ctl_bsdf_result* results) {
+    if (shading_refusal(d, "oracle_bsdf_eval")) return -1;
+    for (uint64_t i = 0; i < n; i++) {
+        const ctl_bsdf_query& q = queries[i];
+        ctl_bsdf_result& r = results[i];
+        r.value[0] = r.value[1] = r.value[2] = 0.0f;
+        r.pdf = 0.0f;
+        r.wo[0] = q.wo[0]; r.wo[1] = q.wo[1]; r.wo[2] = q.wo[2];
+        r.sampled_type = 0xffffffffu;
+        if (q.material >= d->n_materials) continue;
+        const ctl_material& m = d->materials[q.material];
+        BRec b;
+        b.wi = v3(q.wi[0], q.wi[1], q.wi[2]);
+        b.wo = v3(q.wo[0], q.wo[1], q.wo[2]);
+        b.sampledType = 0;
+        b.typeMask = q.type_mask;
+        b.dg.P = v3s(0.0f);
+        b.dg.sys.s = v3(1.0f, 0.0f, 0.0f); b.dg.sys.t = v3(0.0f, 1.0f, 0.0f); b.dg.sys.n = v3(0.0f, 0.0f, 1.0f);
+        b.dg.n = b.dg.sys.n;
+        b.dg.dpdu = b.dg.sys.s; b.dg.dpdv = b.dg.sys.t;
+        b.dg.bary = v2(0.0f, 0.0f);
+        b.dg.uv = v2(q.uv[0], q.uv[1]);
+        Spec v = v3s(0.0f);
+        float pdf = 0.0f;
+        if (q.op == CTL_BSDF_OP_SAMPLE) v = bsdf_sample(d, m, b, pdf, v2(q.sample[0], q.sample[1]));
+        else if (q.op == CTL_BSDF_OP_F) v = bsdf_f(d, m, b, (int)q.measure);
+        else if (q.op == CTL_BSDF_OP_PDF) pdf = bsdf_pdf(d, m, b, (int)q.measure);
+        r.value[0] = v.x; r.value[1] = v.y; r.value[2] = v.z;
+        r.pdf = pdf;
+        r.wo[0] = b.wo.x; r.wo[1] = b.wo.y; r.wo[2] = b.wo.z;
+        r.sampled_type = b.sampledType;
+    }
+    return 0;
+}
 
 // PrimTracer::DoRender as Tracer<false>::DoPass runs it (Integrators/PrimTracer.cu:19-106,
 // 181-233; Kernel/Tracer.h:209-224): clear the image, one primary ray per pixel
 // through the pixel corner, the draw mode's first-hit value added at (x, y).
-// The supported BSDFs have no delta component, so first_non_delta_X == first_X.
+// Without a delta material first_non_delta_X == first_X; with one those modes are
+// refused (their delta bounce loop is not restated).
 static float depth_d3d(float d, float n, float f) {   // DeviceDepthImage::NormalizeDepthD3D (Tracer.h:26-31)
     float z = omin(omax(d, n), f);
     return (f / (f - n) * z - f * n / (f - n)) / z;
@@ -2048,6 +2210,15 @@ static float depth_d3d(float d, float n, float f) {   // DeviceDepthImage::Norma
 
 uint64_t oracle_prim_pass(const ctl_scene_desc* desc, const ctl_prim_params* prm, uint64_t pass_index, ctl_pixel* fb,
                           float* depth, int32_t tie, int32_t threads) {
+    if (shading_refusal(desc, "oracle_prim_pass")) return UINT64_MAX;
+    // the delta bounce loop of the first_non_delta modes is not restated
+    if (prm->draw_mode == CTL_PRIM_FIRST_NON_DELTA_LE || prm->draw_mode == CTL_PRIM_FIRST_NON_DELTA_F ||
+        prm->draw_mode == CTL_PRIM_FIRST_NON_DELTA_F_DIRECT)
+        for (uint32_t i = 0; i < desc->n_materials; i++)
+            if (desc->materials[i].combined_type & EDelta) {
+                set_error("oracle_prim_pass: the first_non_delta draw modes are not restated for scenes with delta materials");
+                return UINT64_MAX;
+            }
     const uint32_t nseq = 4096, len = 30;
     std::vector<float> s1((size_t)nseq * len), s2((size_t)nseq * len * 2);
     sampler_tables(pass_index, nseq, len, s1.data(), s2.data());
@@ -2166,6 +2337,7 @@ void oracle_camera_rays(const ctl_scene_desc* desc, uint64_t pass_index, ctl_ray
 uint64_t oracle_wpt_render_pass(const ctl_scene_desc* desc, int32_t direct, int32_t max_path_length,
                                 int32_t rr_start_depth, uint32_t passes_done, uint64_t pass_index, ctl_pixel* fb,
                                 int32_t tie, int32_t threads) {
+    if (shading_refusal(desc, "oracle_wpt_render_pass")) return UINT64_MAX;
     return wpt_render(desc, direct != 0, max_path_length, rr_start_depth, passes_done, pass_index, fb, tie, threads);
 }
 

@@ -54,11 +54,20 @@ def materials():
         add(ctl.roughconductor_material(dist, GOLD_ETA, GOLD_K, alpha), dict(type=R.ROUGHCONDUCTOR, dist=dist, alpha=alpha))
     for dist, alpha in ((_abi.CTL_MICROFACET_GGX, 0.3), (_abi.CTL_MICROFACET_BECKMANN, 0.25)):
         add(ctl.roughdielectric_material(dist, 1.5, alpha), dict(type=5, dist=dist, alpha=alpha))
+    # appended (the indices above stay): anisotropic rough conductors and a two-sided one
+    for dist, au, av, ts in ((_abi.CTL_MICROFACET_GGX, 0.15, 0.4, False), (_abi.CTL_MICROFACET_BECKMANN, 0.35, 0.12, False),
+                             (_abi.CTL_MICROFACET_GGX, 0.3, 0.2, True)):
+        add(ctl.roughconductor_material(dist, ALU_ETA, ALU_K, au, av, (0.9, 0.95, 1.0), two_sided=ts),
+            dict(type=R.ROUGHCONDUCTOR, dist=dist, alpha=au, alpha_v=av, two_sided=ts, appended=True))
     return A, D
 
 
-def indices_of(type):
-    return [i for i, d in enumerate(materials()[1]) if d is not None and d["type"] == type]
+def indices_of(type, appended=False):
+    """Material indices of a type.  The materials appended later (anisotropic and two-sided rough
+    conductors) are left out unless asked for: the property tests' bounds are derived for the first,
+    isotropic pair."""
+    return [i for i, d in enumerate(materials()[1])
+            if d is not None and d["type"] == type and (appended or not d.get("appended"))]
 
 
 @functools.lru_cache(maxsize=None)
@@ -155,6 +164,25 @@ def delta_queries(type):
     return q
 
 
+@functools.lru_cache(maxsize=None)
+def roughconductor_queries(n=4200):
+    """sample / f / pdf queries over every rough conductor (the appended anisotropic and two-sided
+    ones included): random directions, three quarters of them in the upper hemisphere, the masks
+    EALL, glossy only and delta only, both measures.  BSDF_QUERY_DTYPE array."""
+    rng = np.random.RandomState(3)
+    rc = indices_of(R.ROUGHCONDUCTOR, appended=True)
+    q = np.zeros(n, dtype=ctl.BSDF_QUERY_DTYPE)
+    for i in range(len(q)):
+        d = rng.normal(size=(2, 3))
+        d /= np.linalg.norm(d, axis=1, keepdims=True)
+        if i % 4:
+            d[:, 2] = np.abs(d[:, 2])
+        mask = (R.EALL, R.EGLOSSY_REFLECTION, R.EDELTA_REFLECTION)[0 if i % 5 else (i // 5) % 3]
+        q[i] = (rc[rng.randint(len(rc))], i % 3, mask, R.EDISCRETE if i % 11 == 0 else R.ESOLID_ANGLE, d[0], d[1],
+                rng.uniform(0, 1, 2), (0.5, 0.5))
+    return q
+
+
 def pack(results):
     """bsdf_ref result tuples -> BSDF_RESULT_DTYPE array."""
     out = np.zeros(len(results), dtype=ctl.BSDF_RESULT_DTYPE)
@@ -167,6 +195,33 @@ def reference(q, warp=None):
     _, D = materials()
     return pack([R.bsdfall(D[int(r["material"])], int(r["op"]), r["wi"], r["wo"], int(r["type_mask"]), int(r["measure"]),
                            r["sample"], warp) for r in q])
+
+
+def plastic_reference(q, evaluate):
+    """The restatement's answers to plastic queries, with the cosine warp taken from `evaluate`'s
+    diffuse material (index 0) at the remapped sample.  evaluate: queries -> BSDF_RESULT_DTYPE array.
+    -> (results, number of distinct warps)."""
+    _, D = materials()
+    need = {}
+    for r in q:
+        if int(r["op"]) != 0:
+            continue
+        d = D[int(r["material"])]
+        wi = R.vec(r["wi"])
+        if wi[2] < 0 and d["two_sided"]:
+            wi = (wi[0], wi[1], -wi[2])
+        with np.errstate(all="ignore"):
+            s = R.plastic_remap(d, wi, int(r["type_mask"]), r["sample"])
+        if s is not None:
+            need[(np.float32(s[0]).tobytes(), np.float32(s[1]).tobytes())] = s
+    keys = list(need)
+    wq = np.zeros(len(keys), dtype=ctl.BSDF_QUERY_DTYPE)
+    for i, k in enumerate(keys):
+        wq[i] = (0, 0, R.EALL, R.ESOLID_ANGLE, (0, 0, 1), (0, 0, 1), need[k], (0.5, 0.5))
+    wres = evaluate(wq)
+    table = {k: R.vec(wres[i]["wo"]) for i, k in enumerate(keys)}
+    warp = lambda s: table[(np.float32(s[0]).tobytes(), np.float32(s[1]).tobytes())]   # noqa: E731
+    return reference(q, warp), len(keys)
 
 
 def same_bits(a, b):

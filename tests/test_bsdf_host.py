@@ -38,27 +38,7 @@ def test_delta_types_match_the_restatement_bit_for_bit(type):
 
 def _plastic_reference(q):
     """The restatement with the warp taken from the entry's diffuse material (index 0) at the remapped sample."""
-    _, D = BC.materials()
-    need = {}
-    for r in q:
-        if int(r["op"]) != 0:
-            continue
-        d = D[int(r["material"])]
-        wi = R.vec(r["wi"])
-        if wi[2] < 0 and d["two_sided"]:
-            wi = (wi[0], wi[1], -wi[2])
-        with np.errstate(all="ignore"):
-            s = R.plastic_remap(d, wi, int(r["type_mask"]), r["sample"])
-        if s is not None:
-            need[(np.float32(s[0]).tobytes(), np.float32(s[1]).tobytes())] = s
-    keys = list(need)
-    wq = np.zeros(len(keys), dtype=ctl.BSDF_QUERY_DTYPE)
-    for i, k in enumerate(keys):
-        wq[i] = (0, 0, R.EALL, R.ESOLID_ANGLE, (0, 0, 1), (0, 0, 1), need[k], (0.5, 0.5))
-    wres = _eval(wq)
-    table = {k: R.vec(wres[i]["wo"]) for i, k in enumerate(keys)}
-    warp = lambda s: table[(np.float32(s[0]).tobytes(), np.float32(s[1]).tobytes())]   # noqa: E731
-    return BC.reference(q, warp), len(keys)
+    return BC.plastic_reference(q, _eval)
 
 
 def test_plastic_matches_the_restatement_bit_for_bit():

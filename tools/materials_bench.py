@@ -1,4 +1,4 @@
-"""Throughput of the mixed-material test scene (tests/test_gpu_materials.py::mixed_scene: a diffuse
+"""Throughput of the mixed-material test scene (tests/materials_scenes.py::mixed_scene: a diffuse
 floor, an area light, an environment map and one card each of dielectric, thindielectric, conductor,
 roughconductor and plastic) at 1920 x 1080: PathTracer, Direct = 1, MaxPathLength 50, RRStartDepth 5,
 any-hit shadow rays, passes in one ctl_render_passes launch, device events around the launch.
@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import cudatracerlib_amd as ctl  # noqa: E402
-from test_gpu_materials import mixed_scene  # noqa: E402
+from materials_scenes import mixed_scene  # noqa: E402
 
 
 def main():
