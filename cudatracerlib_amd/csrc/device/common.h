@@ -4,9 +4,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cassert>
 #include <string>
 #include <vector>
 
+#include "dispatch.h"
 #include "traverse.h"
 #include "../ctl_env.h"
 
@@ -453,6 +456,21 @@ enum : int { kShadeLean = 0, kShadeFull = 1, kShadeEnv = 2, kShadeAlpha = 3, kSh
 #define CTL_EXT_OF(F) ((F) == kShadeMat)
 // kernels that never trace (wavefront shade, WPT iterate) share the full instantiation
 #define CTL_NO_TRACE_LEVEL(F) ((F) == kShadeAlpha ? kShadeFull : (F))
+// Host: f(FU) with DevScene::full_shading as a constant (dispatch.h), over the
+// five levels or, for the kernels that never trace, the four they instantiate.
+// full_shading only ever holds one of the five (scene_dev.hip).
+template <class F>
+void with_shade_level(uint32_t full, F&& f) {
+    const bool known = with_level<kShadeLean, kShadeFull, kShadeEnv, kShadeAlpha, kShadeMat>((int)full, f);
+    assert(known);
+    (void)known;
+}
+template <class F>
+void with_no_trace_level(uint32_t full, F&& f) {
+    const bool known = with_level<kShadeLean, kShadeFull, kShadeEnv, kShadeMat>((int)CTL_NO_TRACE_LEVEL(full), f);
+    assert(known);
+    (void)known;
+}
 
 __device__ __forceinline__ EnvView env_view(const DevScene& S) { return EnvView{S.env, S.env_data, S.textures, S.tex_data}; }
 
@@ -835,6 +853,26 @@ int resident_blocks(ctl_ctx* c, K kernel, size_t lds) {
     c->resident.push_back({key, {lds, nb}});
     return nb;
 }
+// The grid of a persistent launch: the resident blocks, at most bpc blocks per
+// CU when bpc > 0, and no more than the `want` blocks the work fills.
+template <class K>
+dim3 resident_grid(ctl_ctx* c, K kernel, size_t lds, uint64_t want, int bpc = 0) {
+    int nb = resident_blocks(c, kernel, lds);
+    if (bpc > 0) nb = std::min(nb, bpc * c->cu_count);
+    return dim3((unsigned)std::min<uint64_t>(nb, want));
+}
+
+// A failed HIP call of a C-ABI function: the call's text (`what`) and HIP's
+// message into the context's error string, CTL_ERR_HIP to the caller.
+#define CTL_HIP_AS(ctx, call, what)                                                        \
+    do {                                                                                   \
+        hipError_t e_ = (call);                                                            \
+        if (e_ != hipSuccess) {                                                            \
+            (ctx)->err = std::string(what) + ": " + hipGetErrorString(e_);                 \
+            return CTL_ERR_HIP;                                                            \
+        }                                                                                  \
+    } while (0)
+#define CTL_HIP(ctx, call) CTL_HIP_AS(ctx, call, #call)
 
 // scene_dev.hip: drops the device scene
 void free_scene(ctl_ctx* c);

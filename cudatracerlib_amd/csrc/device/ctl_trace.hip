@@ -541,15 +541,6 @@ __global__ __launch_bounds__(kBlock) void occluded_kernel(DevScene S_arg, int64_
 static std::mutex g_err_mtx;
 static std::string g_create_err;
 
-#define CTL_HIP(ctx, call)                                                                 \
-    do {                                                                                   \
-        hipError_t e_ = (call);                                                            \
-        if (e_ != hipSuccess) {                                                            \
-            (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_);                \
-            return CTL_ERR_HIP;                                                            \
-        }                                                                                  \
-    } while (0)
-
 extern "C" {
 
 CTL_API int32_t ctl_abi_version(void) { return CTL_ABI_VERSION; }
@@ -699,32 +690,23 @@ static ctl_status launch_intersect(ctl_ctx* c, int64_t n, const ctl_ray* rays, c
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     unsigned long long* cursor = c->d_cursors;
     CTL_HIP(c, hipMemsetAsync(cursor, 0, sizeof(unsigned long long), s));
-    const bool single = c->scene.single != 0;
     const uint64_t want = ((uint64_t)(n + n2) + kBlock - 1) / kBlock;
 #ifndef CTL_INTERSECT_BPC
 #define CTL_INTERSECT_BPC 3   // resident blocks per CU of the batch traversal (0: occupancy limit)
 #endif
-#define IK(AN, ST, SG, WD)                                                                                       \
-    do {                                                                                                         \
-        int nb = resident_blocks(c, intersect_kernel<AN, ST, SG, WD>, kStackLdsBytes);                           \
-        if (CTL_INTERSECT_BPC > 0) nb = std::min(nb, CTL_INTERSECT_BPC * c->cu_count);                          \
-        hipLaunchKernelGGL((intersect_kernel<AN, ST, SG, WD>), dim3((unsigned)std::min<uint64_t>(nb, want)),     \
-                           dim3(kBlock), kStackLdsBytes, s, c->scene, n, rays, hits, n2, rays2, hits2, cursor,  \
-                           c->d_counters, dcount, band_w);                                                       \
-    } while (0)
-    // stats launches count the reference's binary traversal (the roofline's algorithmic bytes)
-    const bool wide = c->scene.wide != 0 && !stats;
-#define IK2(AN, ST)                                                       \
-    do {                                                                  \
-        if (ST) { if (single) IK(AN, true, true, 0); else IK(AN, true, false, 0); } \
-        else if (wide) { if (single) IK(AN, false, true, 1); else IK(AN, false, false, 1); } \
-        else { if (single) IK(AN, false, true, 0); else IK(AN, false, false, 0); } \
-    } while (0)
-    if (stats) { if (any_hit) IK2(1, true); else IK2(0, true); }
-    else if (any_hit == 2) IK2(2, false);   // internal: the WavefrontPathTracer's shadow query segment
-    else { if (any_hit) IK2(1, false); else IK2(0, false); }
-#undef IK2
-#undef IK
+    with_tree(stats, c->scene.single != 0, c->scene.wide != 0, [&](auto ST, auto SG, auto WD) {
+        auto launch = [&](auto AN) {
+            auto k = intersect_kernel<decltype(AN)::value, decltype(ST)::value, decltype(SG)::value,
+                                      decltype(WD)::value>;
+            hipLaunchKernelGGL(k, resident_grid(c, k, kStackLdsBytes, want, CTL_INTERSECT_BPC), dim3(kBlock),
+                               kStackLdsBytes, s, c->scene, n, rays, hits, n2, rays2, hits2, cursor, c->d_counters,
+                               dcount, band_w);
+        };
+        // 2 is internal: the WavefrontPathTracer's shadow query segment; a stats launch counts it as any-hit
+        if (any_hit == 2 && !decltype(ST)::value) launch(std::integral_constant<int, 2>{});
+        else if (any_hit) launch(std::integral_constant<int, 1>{});
+        else launch(std::integral_constant<int, 0>{});
+    });
     CTL_HIP(c, hipGetLastError());
     return CTL_OK;
 }
@@ -752,14 +734,13 @@ CTL_API ctl_status ctl_occluded(ctl_ctx* c, int64_t n, const ctl_ray* d_rays, ui
         c->err = "occluded: batch too large for one launch";
         return CTL_ERR_INVALID;
     }
-    const bool single = c->scene.single != 0, wide = c->scene.wide != 0;
-#define OK_(AQ, SG, WD) hipLaunchKernelGGL((occluded_kernel<AQ, SG, WD>), grid, dim3(kBlock), kStackLdsBytes, s, \
-                                           c->scene, n, d_rays, d_out, c->d_counters)
-#define OK2(AQ) do { if (wide) { if (single) OK_(AQ, true, 1); else OK_(AQ, false, 1); } \
-                     else { if (single) OK_(AQ, true, 0); else OK_(AQ, false, 0); } } while (0)
-    if (any_hit) OK2(true); else OK2(false);
-#undef OK2
-#undef OK_
+    with_tree(c->scene.single != 0, c->scene.wide != 0, [&](auto SG, auto WD) {
+        auto launch = [&](auto AQ) {
+            hipLaunchKernelGGL((occluded_kernel<decltype(AQ)::value, decltype(SG)::value, decltype(WD)::value>), grid,
+                               dim3(kBlock), kStackLdsBytes, s, c->scene, n, d_rays, d_out, c->d_counters);
+        };
+        if (any_hit) launch(std::true_type{}); else launch(std::false_type{});
+    });
     CTL_HIP(c, hipGetLastError());
     return add_rays(c, (uint64_t)n, s);   // each Occluded is one traceRay (TraceHelper.cu:176)
 }
@@ -837,44 +818,29 @@ static ctl_status launch_schedule(ctl_ctx* c, const ctl_pt_params* p, const Path
                                   hipStream_t s, uint64_t threads, dim3 grid, const float* s1, const float2* s2,
                                   SampleSlots PS, uint32_t tbl) {
     if (p->flags & CTL_PT_WAVEFRONT) return (ctl_status)ctl::wavefront_pass(c, P, PS, stats, s);
-    const bool single = c->scene.single != 0;
-    // stats launches count the reference's binary traversal (the roofline's algorithmic bytes)
-    const bool wide = c->scene.wide != 0 && !stats;
-    const uint32_t full = c->scene.full_shading;
-    if (!(p->flags & CTL_PT_MEGAKERNEL)) {
-        unsigned long long* cursor = c->d_cursors + 1;
-        CTL_HIP(c, hipMemsetAsync(cursor, 0, sizeof(unsigned long long), s));
-        const uint64_t want = (threads + kBlock - 1) / kBlock;
+    const bool persistent = !(p->flags & CTL_PT_MEGAKERNEL);
+    unsigned long long* cursor = c->d_cursors + 1;
+    if (persistent) CTL_HIP(c, hipMemsetAsync(cursor, 0, sizeof(unsigned long long), s));
+    const uint64_t want = (threads + kBlock - 1) / kBlock;
 #ifndef CTL_PERSIST_BPC
 #define CTL_PERSIST_BPC 0   // resident blocks per CU of the persistent path kernel (0: occupancy limit)
 #endif
-#define PK(ST, SG, WD, FU)                                                                                       \
-        do {                                                                                                     \
-            constexpr size_t lds = persistent_lds_bytes();                                                      \
-            int nb = resident_blocks(c, path_kernel_persistent<ST, SG, WD, FU>, lds);                            \
-            if (CTL_PERSIST_BPC > 0) nb = std::min(nb, CTL_PERSIST_BPC * c->cu_count);                          \
-            hipLaunchKernelGGL((path_kernel_persistent<ST, SG, WD, FU>), dim3((unsigned)std::min<uint64_t>(nb, want)), \
-                               dim3(kBlock), lds, s, c->scene, P, s1, s2, threads, cursor,                       \
-                               c->d_counters, PS, tbl);                                                          \
-        } while (0)
-#define PK2(ST, SG, WD) do { if (full == kShadeMat) PK(ST, SG, WD, kShadeMat); else if (full == kShadeEnv) PK(ST, SG, WD, kShadeEnv); else if (full == kShadeAlpha) PK(ST, SG, WD, kShadeAlpha); \
-                              else if (full) PK(ST, SG, WD, kShadeFull); else PK(ST, SG, WD, kShadeLean); } while (0)
-        if (stats) { if (single) PK2(true, true, 0); else PK2(true, false, 0); }
-        else if (wide) { if (single) PK2(false, true, 1); else PK2(false, false, 1); }
-        else { if (single) PK2(false, true, 0); else PK2(false, false, 0); }
-#undef PK2
-#undef PK
-    } else {
-#define MK(ST, SG, WD, FU) hipLaunchKernelGGL((path_kernel<ST, SG, WD, FU>), grid, dim3(kBlock), kStackLdsBytes, s, c->scene, \
-                                              P, s1, s2, fb, c->d_counters, PS)
-#define MK2(ST, SG, WD) do { if (full == kShadeMat) MK(ST, SG, WD, kShadeMat); else if (full == kShadeEnv) MK(ST, SG, WD, kShadeEnv); else if (full == kShadeAlpha) MK(ST, SG, WD, kShadeAlpha); \
-                              else if (full) MK(ST, SG, WD, kShadeFull); else MK(ST, SG, WD, kShadeLean); } while (0)
-        if (stats) { if (single) MK2(true, true, 0); else MK2(true, false, 0); }
-        else if (wide) { if (single) MK2(false, true, 1); else MK2(false, false, 1); }
-        else { if (single) MK2(false, true, 0); else MK2(false, false, 0); }
-#undef MK2
-#undef MK
-    }
+    with_tree(stats, c->scene.single != 0, c->scene.wide != 0, [&](auto ST, auto SG, auto WD) {
+        with_shade_level(c->scene.full_shading, [&](auto FU) {
+            if (persistent) {
+                constexpr size_t lds = persistent_lds_bytes();
+                auto k = path_kernel_persistent<decltype(ST)::value, decltype(SG)::value, decltype(WD)::value,
+                                                decltype(FU)::value>;
+                hipLaunchKernelGGL(k, resident_grid(c, k, lds, want, CTL_PERSIST_BPC), dim3(kBlock), lds, s, c->scene,
+                                   P, s1, s2, threads, cursor, c->d_counters, PS, tbl);
+            } else {
+                auto k = path_kernel<decltype(ST)::value, decltype(SG)::value, decltype(WD)::value,
+                                     decltype(FU)::value>;
+                hipLaunchKernelGGL(k, grid, dim3(kBlock), kStackLdsBytes, s, c->scene, P, s1, s2, fb, c->d_counters,
+                                   PS);
+            }
+        });
+    });
     CTL_HIP(c, hipGetLastError());
     return CTL_OK;
 }
@@ -1222,27 +1188,18 @@ CTL_API ctl_status ctl_render_pass_blocks(ctl_ctx* c, const ctl_pt_params* p, co
     if (r != CTL_OK) return r;
     unsigned long long* cursor = c->d_cursors + 1;
     CTL_HIP(c, hipMemsetAsync(cursor, 0, sizeof(unsigned long long), s));
-    const bool single = c->scene.single != 0, wide = c->scene.wide != 0;
-    const uint32_t full = c->scene.full_shading;
     const uint64_t want = (items + kBlock - 1) / kBlock;
     const SampleSlots PS = make_slots(c->d_slices, (uint32_t)items);
     const float* s1 = c->d_s1[c->active];
     const float2* s2 = c->d_s2[c->active];
-#define PKL(SG, WD, FU)                                                                                          \
-    do {                                                                                                         \
-        constexpr size_t lds = persistent_lds_bytes();                                                          \
-        int nb = resident_blocks(c, path_kernel_persistent_blocks<SG, WD, FU>, lds);                             \
-        if (CTL_PERSIST_BPC > 0) nb = std::min(nb, CTL_PERSIST_BPC * c->cu_count);                              \
-        hipLaunchKernelGGL((path_kernel_persistent_blocks<SG, WD, FU>),                                          \
-                           dim3((unsigned)std::min<uint64_t>(nb, want)), dim3(kBlock), lds, s, c->scene, P, s1,  \
-                           s2, items, cursor, c->d_counters, PS, (const uint32_t*)c->d_block_tbl);               \
-    } while (0)
-#define PKL2(SG, WD) do { if (full == kShadeMat) PKL(SG, WD, kShadeMat); else if (full == kShadeEnv) PKL(SG, WD, kShadeEnv); else if (full == kShadeAlpha) PKL(SG, WD, kShadeAlpha); \
-                          else if (full) PKL(SG, WD, kShadeFull); else PKL(SG, WD, kShadeLean); } while (0)
-    if (wide) { if (single) PKL2(true, 1); else PKL2(false, 1); }
-    else { if (single) PKL2(true, 0); else PKL2(false, 0); }
-#undef PKL2
-#undef PKL
+    with_tree(c->scene.single != 0, c->scene.wide != 0, [&](auto SG, auto WD) {
+        with_shade_level(c->scene.full_shading, [&](auto FU) {
+            constexpr size_t lds = persistent_lds_bytes();
+            auto k = path_kernel_persistent_blocks<decltype(SG)::value, decltype(WD)::value, decltype(FU)::value>;
+            hipLaunchKernelGGL(k, resident_grid(c, k, lds, want, CTL_PERSIST_BPC), dim3(kBlock), lds, s, c->scene, P,
+                               s1, s2, items, cursor, c->d_counters, PS, (const uint32_t*)c->d_block_tbl);
+        });
+    });
     CTL_HIP(c, hipGetLastError());
     hipLaunchKernelGGL(fold_blocks_kernel, dim3((unsigned)((own + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, P,
                        (const uint32_t*)c->d_block_tbl, (const float4*)c->d_slices, d_fb);
@@ -1351,15 +1308,23 @@ static ctl_status read_stats(ctl_ctx* c, uint64_t out[4], uint64_t rays_before, 
     return CTL_OK;
 }
 
+// Opens a stats call: waits for the stream, clears the statistics counters
+// [2..4] and reads the ray count the call starts from (read_stats closes it).
+static ctl_status begin_stats(ctl_ctx* c, unsigned long long& before, hipStream_t s) {
+    CTL_HIP(c, hipStreamSynchronize(s));
+    CTL_HIP(c, hipMemset(c->d_counters + 2, 0, 3 * sizeof(unsigned long long)));
+    CTL_HIP(c, hipMemcpy(&before, c->d_counters, sizeof(before), hipMemcpyDeviceToHost));
+    return CTL_OK;
+}
+
 CTL_API ctl_status ctl_intersect_stats(ctl_ctx* c, int64_t n, const ctl_ray* d_rays, ctl_hit* d_hits, int32_t any_hit,
                                        uint64_t out[4], void* stream) {
     if (!c || !out) return CTL_ERR_INVALID;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     unsigned long long before = 0;
-    CTL_HIP(c, hipStreamSynchronize(s));
-    CTL_HIP(c, hipMemset(c->d_counters + 2, 0, 3 * sizeof(unsigned long long)));
-    CTL_HIP(c, hipMemcpy(&before, c->d_counters, sizeof(before), hipMemcpyDeviceToHost));
-    ctl_status r = launch_intersect(c, n, d_rays, d_hits, any_hit ? 1 : 0, true, stream);
+    ctl_status r = begin_stats(c, before, s);
+    if (r != CTL_OK) return r;
+    r = launch_intersect(c, n, d_rays, d_hits, any_hit ? 1 : 0, true, stream);
     if (r != CTL_OK) return r;
     if ((r = add_rays(c, (uint64_t)n, s)) != CTL_OK) return r;
     return read_stats(c, out, before, s);
@@ -1370,10 +1335,9 @@ CTL_API ctl_status ctl_render_pass_stats(ctl_ctx* c, const ctl_pt_params* params
     if (!c || !out) return CTL_ERR_INVALID;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     unsigned long long before = 0;
-    CTL_HIP(c, hipStreamSynchronize(s));
-    CTL_HIP(c, hipMemset(c->d_counters + 2, 0, 3 * sizeof(unsigned long long)));
-    CTL_HIP(c, hipMemcpy(&before, c->d_counters, sizeof(before), hipMemcpyDeviceToHost));
-    ctl_status r = launch_pass(c, params, d_fb, true, stream);
+    ctl_status r = begin_stats(c, before, s);
+    if (r != CTL_OK) return r;
+    r = launch_pass(c, params, d_fb, true, stream);
     if (r != CTL_OK) return r;
     return read_stats(c, out, before, s);
 }

@@ -145,15 +145,6 @@ static_assert(kBlock == 256, "block_stats_kernel adds four wave sums");
 
 using namespace ctl;
 
-#define CTL_HIP(ctx, call)                                                                 \
-    do {                                                                                   \
-        hipError_t e_ = (call);                                                            \
-        if (e_ != hipSuccess) {                                                            \
-            (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_);                \
-            return CTL_ERR_HIP;                                                            \
-        }                                                                                  \
-    } while (0)
-
 extern "C" {
 
 CTL_API ctl_status ctl_image_resolve(ctl_ctx* c, const ctl_pixel* fb, uint32_t w, uint32_t h, float splat,

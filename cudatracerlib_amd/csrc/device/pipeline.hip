@@ -379,15 +379,6 @@ void image_free(ctl_ctx* c) {
 
 using namespace ctl;
 
-#define CTL_HIP(ctx, call)                                                                 \
-    do {                                                                                   \
-        hipError_t e_ = (call);                                                            \
-        if (e_ != hipSuccess) {                                                            \
-            (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_);                \
-            return CTL_ERR_HIP;                                                            \
-        }                                                                                  \
-    } while (0)
-
 namespace {
 
 inline unsigned blocks_of(uint64_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }

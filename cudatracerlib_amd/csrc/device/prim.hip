@@ -172,15 +172,6 @@ void prim_kernel(DevScene S_arg, PathParams P_arg, PrimParams Q, const float* s1
 
 }  // namespace
 
-#define CTL_HIP(ctx, call)                                                                 \
-    do {                                                                                   \
-        hipError_t e_ = (call);                                                            \
-        if (e_ != hipSuccess) {                                                            \
-            (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_);                \
-            return CTL_ERR_HIP;                                                            \
-        }                                                                                  \
-    } while (0)
-
 extern "C" {
 
 CTL_API ctl_status ctl_prim_pass(ctl_ctx* c, const ctl_prim_params* p, ctl_pixel* d_fb, float* d_depth,
@@ -216,22 +207,15 @@ CTL_API ctl_status ctl_prim_pass(ctl_ctx* c, const ctl_prim_params* p, ctl_pixel
     CTL_HIP(c, hipMemsetAsync(d_fb, 0, sizeof(ctl_pixel) * (size_t)cam.width * cam.height, s));
     unsigned long long* cursor = c->d_cursors + 2;
     CTL_HIP(c, hipMemsetAsync(cursor, 0, sizeof(unsigned long long), s));
-    const bool single = c->scene.single != 0, wide = c->scene.wide != 0;
-    const uint32_t full = c->scene.full_shading;
     const uint64_t want = (items + kBlock - 1) / kBlock;
-#define PRK(SG, WD, FU)                                                                                          \
-    do {                                                                                                         \
-        const int nb = resident_blocks(c, prim_kernel<SG, WD, FU>, kStackLdsBytes);                              \
-        hipLaunchKernelGGL((prim_kernel<SG, WD, FU>), dim3((unsigned)std::min<uint64_t>(nb, want)), dim3(kBlock), \
-                           kStackLdsBytes, s, c->scene, P, Q, c->d_s1[c->active], c->d_s2[c->active], items,     \
-                           cursor, c->d_counters, d_fb, d_depth);                                                \
-    } while (0)
-#define PRK2(SG, WD) do { if (full == kShadeMat) PRK(SG, WD, kShadeMat); else if (full == kShadeEnv) PRK(SG, WD, kShadeEnv); else if (full == kShadeAlpha) PRK(SG, WD, kShadeAlpha); \
-                           else if (full) PRK(SG, WD, kShadeFull); else PRK(SG, WD, kShadeLean); } while (0)
-    if (wide) { if (single) PRK2(true, 1); else PRK2(false, 1); }
-    else { if (single) PRK2(true, 0); else PRK2(false, 0); }
-#undef PRK2
-#undef PRK
+    with_tree(c->scene.single != 0, c->scene.wide != 0, [&](auto SG, auto WD) {
+        with_shade_level(c->scene.full_shading, [&](auto FU) {
+            auto k = prim_kernel<decltype(SG)::value, decltype(WD)::value, decltype(FU)::value>;
+            hipLaunchKernelGGL(k, resident_grid(c, k, kStackLdsBytes, want), dim3(kBlock), kStackLdsBytes, s, c->scene,
+                               P, Q, c->d_s1[c->active], c->d_s2[c->active], items, cursor, c->d_counters, d_fb,
+                               d_depth);
+        });
+    });
     CTL_HIP(c, hipGetLastError());
     CTL_HIP(c, hipEventRecord(c->pass_ev[1], s));
     c->pass_timed = true;

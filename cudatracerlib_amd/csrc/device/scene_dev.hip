@@ -34,14 +34,7 @@ using namespace ctl;
 
 namespace {
 
-#define SD_HIP(ctx, call)                                                                  \
-    do {                                                                                   \
-        hipError_t e_ = (call);                                                            \
-        if (e_ != hipSuccess) {                                                            \
-            (ctx)->err = std::string("scene: ") + #call + ": " + hipGetErrorString(e_);    \
-            return CTL_ERR_HIP;                                                            \
-        }                                                                                  \
-    } while (0)
+#define SD_HIP(ctx, call) CTL_HIP_AS(ctx, call, "scene: " #call)
 
 constexpr uint32_t kDirtyTrees = CTL_DIRTY_BVH | CTL_DIRTY_NODES;
 

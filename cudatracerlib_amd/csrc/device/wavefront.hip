@@ -164,21 +164,18 @@ __global__ __launch_bounds__(kBlock) void wf_trace_kernel(DevScene S_arg, WfStat
 template <int MODE>
 void launch_trace(ctl_ctx* c, hipStream_t s, const uint32_t* queue, const uint32_t* cnt, uint32_t* cursor, bool stats) {
     WfState& W = c->wf;
-    const bool single = c->scene.single != 0;
-#define LT(ST, SG, WD, AL)                                                                                      \
-    do {                                                                                                        \
-        const int blocks = resident_blocks(c, wf_trace_kernel<MODE, ST, SG, WD, AL>, kStackLdsBytes);           \
-        hipLaunchKernelGGL((wf_trace_kernel<MODE, ST, SG, WD, AL>), dim3(blocks), dim3(kBlock), kStackLdsBytes, s, \
-                           c->scene, W, queue, cnt, cursor, c->d_counters);                                     \
-    } while (0)
-#define LT2(SG, WD) do { if (alpha) LT(false, SG, WD, true); else LT(false, SG, WD, false); } while (0)
-    const bool wide = c->scene.wide != 0 && !stats;   // stats: the reference's binary traversal
-    const bool alpha = c->scene.alpha != 0;
-    if (stats) { if (single) LT(true, true, 0, false); else LT(true, false, 0, false); }
-    else if (wide) { if (single) LT2(true, 1); else LT2(false, 1); }
-    else { if (single) LT2(true, 0); else LT2(false, 0); }
-#undef LT2
-#undef LT
+    with_tree(stats, c->scene.single != 0, c->scene.wide != 0, [&](auto ST, auto SG, auto WD) {
+        // the whole resident grid: the queue's length is known on the device only
+        auto launch = [&](auto AL) {
+            auto k = wf_trace_kernel<MODE, decltype(ST)::value, decltype(SG)::value, decltype(WD)::value,
+                                     decltype(AL)::value>;
+            hipLaunchKernelGGL(k, dim3(resident_blocks(c, k, kStackLdsBytes)), dim3(kBlock), kStackLdsBytes, s,
+                               c->scene, W, queue, cnt, cursor, c->d_counters);
+        };
+        // a stats launch has no alpha-tested variant
+        if constexpr (!decltype(ST)::value) { if (c->scene.alpha != 0) return launch(std::true_type{}); }
+        launch(std::false_type{});
+    });
 }
 
 template <int FULL>
@@ -329,14 +326,10 @@ int wavefront_pass(ctl_ctx* c, const PathParams& P, const SampleSlots& SS, bool 
     for (int b = 0; b < maxB; b++) {
         const uint32_t* cnt = &W.counts[2 * b];
         launch_trace<0>(c, s, W.q[b & 1], cnt, &cursors[2 * b], stats);
-        if (c->scene.full_shading == kShadeMat)
-            hipLaunchKernelGGL((wf_shade_kernel<kShadeMat>), dim3(persist), dim3(kBlock), 0, s, c->scene, P, s1, s2, W, b, SS);
-        else if (CTL_NO_TRACE_LEVEL(c->scene.full_shading) == kShadeEnv)
-            hipLaunchKernelGGL((wf_shade_kernel<kShadeEnv>), dim3(persist), dim3(kBlock), 0, s, c->scene, P, s1, s2, W, b, SS);
-        else if (c->scene.full_shading)
-            hipLaunchKernelGGL((wf_shade_kernel<kShadeFull>), dim3(persist), dim3(kBlock), 0, s, c->scene, P, s1, s2, W, b, SS);
-        else
-            hipLaunchKernelGGL((wf_shade_kernel<kShadeLean>), dim3(persist), dim3(kBlock), 0, s, c->scene, P, s1, s2, W, b, SS);
+        with_no_trace_level(c->scene.full_shading, [&](auto FU) {
+            hipLaunchKernelGGL((wf_shade_kernel<decltype(FU)::value>), dim3(persist), dim3(kBlock), 0, s, c->scene, P,
+                               s1, s2, W, b, SS);
+        });
         const uint32_t* scnt = &W.counts[2 * b + 1];
         if (P.shadow_any_hit) launch_trace<1>(c, s, W.sq, scnt, &cursors[2 * b + 1], stats);
         else launch_trace<2>(c, s, W.sq, scnt, &cursors[2 * b + 1], stats);

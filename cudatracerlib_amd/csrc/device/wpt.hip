@@ -417,14 +417,7 @@ bool wpt_alloc(WptBuffers* B, T** p, size_t n) {
     return true;
 }
 
-#define WPT_HIP(call)                                                          \
-    do {                                                                       \
-        hipError_t e_ = (call);                                                \
-        if (e_ != hipSuccess) {                                                \
-            c->err = std::string("wpt: ") + #call + ": " + hipGetErrorString(e_); \
-            return CTL_ERR_HIP;                                                \
-        }                                                                      \
-    } while (0)
+#define WPT_HIP(call) CTL_HIP_AS(c, call, "wpt: " #call)
 
 }  // namespace
 
@@ -491,7 +484,6 @@ int wpt_pass(ctl_ctx* c, const ctl_wpt_params* prm, ctl_pixel* fb, hipStream_t s
     const float* s1 = c->d_s1[c->active];
     const float2* s2 = c->d_s2[c->active];
     const bool nee = prm->direct != 0;
-    const uint32_t full = CTL_NO_TRACE_LEVEL(c->scene.full_shading);
 
     // count slots for every bounce of the pass (+1 for the last scan's output)
     const uint32_t slots = (uint32_t)prm->max_path_length + 1u;
@@ -547,12 +539,14 @@ int wpt_pass(ctl_ctx* c, const ctl_wpt_params* prm, ctl_pixel* fb, hipStream_t s
                                  depth == 0 && (uint64_t)n0 == (uint64_t)A.width * A.height ? A.width : 0u);
         if (r != CTL_OK) return r;
         A.depth = depth;
-#define WPT_IT(NE, FU)                                                                                             \
-    hipLaunchKernelGGL((wpt_iterate_kernel<NE, FU>), dim3(nb), dim3(kBlock), 0, s, c->scene, A, s1, s2, cnt,      \
-                       B->pay[cur], B->rays[cur], B->hits, B->sec_hits, B->sec_tmp, B->flags, B->blocks, fb)
-        if (nee) { if (full == kShadeMat) WPT_IT(true, kShadeMat); else if (full == kShadeEnv) WPT_IT(true, kShadeEnv); else if (full) WPT_IT(true, kShadeFull); else WPT_IT(true, kShadeLean); }
-        else { if (full == kShadeMat) WPT_IT(false, kShadeMat); else if (full == kShadeEnv) WPT_IT(false, kShadeEnv); else if (full) WPT_IT(false, kShadeFull); else WPT_IT(false, kShadeLean); }
-#undef WPT_IT
+        with_no_trace_level(c->scene.full_shading, [&](auto FU) {
+            auto launch = [&](auto NE) {
+                auto k = wpt_iterate_kernel<decltype(NE)::value, decltype(FU)::value>;
+                hipLaunchKernelGGL(k, dim3(nb), dim3(kBlock), 0, s, c->scene, A, s1, s2, cnt, B->pay[cur], B->rays[cur],
+                                   B->hits, B->sec_hits, B->sec_tmp, B->flags, B->blocks, fb);
+            };
+            if (nee) launch(std::true_type{}); else launch(std::false_type{});
+        });
         hipLaunchKernelGGL(wpt_scan_kernel, dim3(1), dim3(kScanThreads), 0, s, B->blocks, cnt, B->counts + 2 * (depth + 1));
         hipLaunchKernelGGL(wpt_scatter_kernel, dim3(nb), dim3(kBlock), 0, s, cnt, B->flags, B->blocks, B->pay[cur],
                            B->rays[cur], B->sec_tmp, B->pay[1 - cur], B->rays[1 - cur], B->sec);

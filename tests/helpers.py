@@ -212,6 +212,50 @@ def grid_room(ctl, offset, n=24, size=4.0, w=64, h=64):
     return s, s.compile()
 
 
+_ALPHA = {}
+
+
+def alpha_scene(ctl):
+    """A checker alpha map (alpha channel), a luminance-thresholded texture and a
+    reflectance-map alpha quad in front of a lit wall, camera 96 x 64: a one-level
+    scene of the kShadeAlpha level.  Returns (desc, materials); the host scene
+    that owns the desc's arrays is kept here."""
+    if "d" in _ALPHA:
+        return _ALPHA["d"], _ALPHA["mats"]
+    s = ctl.HostScene()
+    yy, xx = np.mgrid[0:64, 0:64]
+    chk = (((xx // 8) + (yy // 8)) % 2).astype(np.uint32)
+    img = (200 | (180 << 8) | (90 << 16) | ((chk * 255) << 24)).astype(np.uint32)
+    lum = ((xx * 4) | ((yy * 4) << 8) | (128 << 16) | (255 << 24)).astype(np.uint32)
+    ta = s.add_texture(img, filter=ctl._abi.CTL_TEX_BILINEAR)
+    tl = s.add_texture(lum, filter=ctl._abi.CTL_TEX_POINT, mapping=(2.0, 0.0, 0.0, 0.0, 2.0, 0.0))
+    m_alpha = ctl.set_alpha_map(ctl.diffuse_material(0.7, 0.3, 0.2), 2, 0.5, ta)
+    m_lum = ctl.set_alpha_map(ctl.diffuse_material(0.2, 0.6, 0.3), 1, 0.35, tl)
+    m_refl = ctl.set_alpha_map(ctl.diffuse_material(0.5, 0.5, 0.5, texture=ta), 6, 0.5)
+    wall, light = ctl.diffuse_material(0.8, 0.8, 0.8), ctl.diffuse_material(0.8, 0.8, 0.8)
+    mats = [m_alpha, m_lum, m_refl, wall, light]
+    verts, idx, mi, uv = [], [], [], []
+
+    def quad(p, k, uvs=((0, 0), (1, 0), (1, 1), (0, 1))):
+        b = len(verts)
+        verts.extend(p)
+        uv.extend(uvs)
+        idx.extend([(b, b + 1, b + 2), (b, b + 2, b + 3)])
+        mi.extend([k, k])
+
+    for k, x0 in enumerate((-2.2, -0.7, 0.8)):
+        quad([(x0, -1, 0), (x0 + 1.4, -1, 0), (x0 + 1.4, 1, 0), (x0, 1, 0)], k)
+    quad([(-4, -3, 2), (4, -3, 2), (4, 3, 2), (-4, 3, 2)], 3)
+    quad([(-1, 3, -3), (-1, 3, -1), (1, 3, -1), (1, 3, -3)], 4)
+    m = s.add_mesh(np.array(verts, np.float32), np.array(idx, np.uint32), mats, mat_index=np.array(mi, np.uint8),
+                   uvs=np.array(uv, np.float32))
+    node = s.add_node(m)
+    s.add_area_light(node, 4, (30.0, 30.0, 30.0))
+    s.set_camera((0.2, 0.1, -5.0), (0, 0, 0), (0, 1, 0), 55.0, 96, 64)
+    _ALPHA.update(s=s, d=s.compile(), mats=mats)
+    return _ALPHA["d"], mats
+
+
 def grazing_rays(desc, offset, n, seed, size=4.0):
     """Rays starting on (or 1e-4 off) the room's walls, nearly parallel to the
     wall they start on (that axis' direction component scaled by 1e-7..1e-2)."""

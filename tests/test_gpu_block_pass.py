@@ -9,7 +9,7 @@ import pytest
 
 import oracle
 from adaptive_helpers import block_of_pixel, differing, masked, num_blocks, prefill, snapshots
-from helpers import jitter_landing, select_bvh
+from helpers import alpha_scene, binary_bvh, jitter_landing, select_bvh
 
 pytestmark = pytest.mark.gpu
 
@@ -146,9 +146,13 @@ def env_scene_96(ctl):
     return SCENES["env"][1]
 
 
-@pytest.mark.parametrize("which", ["c5", "env"])
+# c5, env, alpha: the shading levels above lean (materials_oracle's block-list test runs the
+# mat level); two-level: the Cornell box, one node per shape, in the reference's binary order
+@pytest.mark.parametrize("which", ["c5", "env", "alpha", "two-level"])
 def test_full_shading_kernels(ctl, orc, tracer, dev, which):
-    d = c5_scene(ctl) if which == "c5" else env_scene_96(ctl)
+    d = {"c5": c5_scene, "env": env_scene_96, "alpha": lambda c: alpha_scene(c)[0],
+         "two-level": lambda c: binary_bvh(scene(c, 1, 1.0, 96, 64))}[which](ctl)
+    assert (d.scene_start_node >= 0) == (which == "two-level")
     p = ctl.PTParams(1, 8, 3, 1, TS, 1, 0, 0)
     pre = prefill(96, 64, seed=11)
     snaps, _ = snapshots(orc, d, p, 2, pre, 1)

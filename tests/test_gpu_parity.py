@@ -8,7 +8,8 @@ import numpy as np
 import pytest
 
 import oracle
-from helpers import binary_bvh, camera_rays, oracle_intersect, oracle_render, random_rays, select_bvh, tie_rule
+from helpers import (alpha_scene, binary_bvh, camera_rays, oracle_intersect, oracle_render, random_rays, select_bvh,
+                     tie_rule)
 
 pytestmark = pytest.mark.gpu
 
@@ -229,6 +230,29 @@ def test_stats_counts(ctl, orc, tracer, dev):
     assert st[1] >= ost[1] * 0.9 and st[2] >= ost[2] * 0.9 and st[3] == ost[3]
 
 
+@pytest.mark.parametrize("config,scale,w,h", [(1, 1.0, 64, 64), (2, 0.25, 96, 64)])   # two-level, one-level
+@pytest.mark.parametrize("mode", ["persistent", "wavefront", "megakernel"])
+def test_render_pass_stats_bit_exact(ctl, orc, tracer, dev, config, scale, w, h, mode):
+    """ctl_render_pass_stats on a scene uploaded with its 4-wide trees: a stats
+    pass runs the reference's binary traversal, so its framebuffer and ray count
+    are the oracle's for the binary order, and it counts nodes and triangles."""
+    d = scene(ctl, config, scale, w, h)
+    assert not d.flags & 2 and (d.scene_start_node >= 0) == (config == 1)
+    p = ctl.PTParams(1, 50, 5, 1, 64, 1, 0, {"persistent": 0, "megakernel": ctl.CTL_PT_MEGAKERNEL,
+                                             "wavefront": ctl.CTL_PT_WAVEFRONT}[mode])
+    want, wrays = oracle_render(orc, binary_bvh(d), p, 1, w, h, first_pass=2)
+    tracer.upload_scene(d)
+    tracer.params = p
+    fb = torch.zeros((w * h, 7), dtype=torch.float32, device=dev)
+    tracer.reset_rays()
+    st = tracer.pass_stats(fb.data_ptr(), 2)
+    assert st[0] == wrays == tracer.rays_traced()
+    assert st[1] > 0 and st[2] > 0
+    got = fb.cpu().numpy()
+    bad = np.nonzero((want.view(np.uint32) != got.view(np.uint32)).any(axis=1))[0]
+    assert bad.size == 0, (bad[:10], want[bad[:3]], got[bad[:3]])
+
+
 def test_full_size_c2_pass_properties(ctl, orc, tracer, dev):
     """BASELINE configs[1] at full size (100k tris, 1280x720): one pass; sampled
     pixels bit-exact against the oracle (every 97th pixel)."""
@@ -421,37 +445,8 @@ def test_render_alpha_tested_traversal(ctl, orc, tracer, dev, mode, bvh):
     a checker alpha map (alpha channel), a luminance-thresholded texture and a
     reflectance-map alpha quad in front of a lit wall; camera, bounce and
     shadow rays all see through the cut-outs.  Bit-exact framebuffers."""
-    s = ctl.HostScene()
-    yy, xx = np.mgrid[0:64, 0:64]
-    chk = (((xx // 8) + (yy // 8)) % 2).astype(np.uint32)
-    img = (200 | (180 << 8) | (90 << 16) | ((chk * 255) << 24)).astype(np.uint32)
-    lum = ((xx * 4) | ((yy * 4) << 8) | (128 << 16) | (255 << 24)).astype(np.uint32)
-    ta = s.add_texture(img, filter=ctl._abi.CTL_TEX_BILINEAR)
-    tl = s.add_texture(lum, filter=ctl._abi.CTL_TEX_POINT, mapping=(2.0, 0.0, 0.0, 0.0, 2.0, 0.0))
-    m_alpha = ctl.set_alpha_map(ctl.diffuse_material(0.7, 0.3, 0.2), 2, 0.5, ta)
-    m_lum = ctl.set_alpha_map(ctl.diffuse_material(0.2, 0.6, 0.3), 1, 0.35, tl)
-    m_refl = ctl.set_alpha_map(ctl.diffuse_material(0.5, 0.5, 0.5, texture=ta), 6, 0.5)
-    wall, light = ctl.diffuse_material(0.8, 0.8, 0.8), ctl.diffuse_material(0.8, 0.8, 0.8)
-    mats = [m_alpha, m_lum, m_refl, wall, light]
-    verts, idx, mi, uv = [], [], [], []
-
-    def quad(p, k, uvs=((0, 0), (1, 0), (1, 1), (0, 1))):
-        b = len(verts)
-        verts.extend(p)
-        uv.extend(uvs)
-        idx.extend([(b, b + 1, b + 2), (b, b + 2, b + 3)])
-        mi.extend([k, k])
-
-    for k, x0 in enumerate((-2.2, -0.7, 0.8)):
-        quad([(x0, -1, 0), (x0 + 1.4, -1, 0), (x0 + 1.4, 1, 0), (x0, 1, 0)], k)
-    quad([(-4, -3, 2), (4, -3, 2), (4, 3, 2), (-4, 3, 2)], 3)
-    quad([(-1, 3, -3), (-1, 3, -1), (1, 3, -1), (1, 3, -3)], 4)
-    m = s.add_mesh(np.array(verts, np.float32), np.array(idx, np.uint32), mats, mat_index=np.array(mi, np.uint8),
-                   uvs=np.array(uv, np.float32))
-    node = s.add_node(m)
-    s.add_area_light(node, 4, (30.0, 30.0, 30.0))
-    s.set_camera((0.2, 0.1, -5.0), (0, 0, 0), (0, 1, 0), 55.0, 96, 64)
-    d = select_bvh(s.compile(), bvh)
+    d0, mats = alpha_scene(ctl)
+    d = select_bvh(d0, bvh)
     p = ctl.PTParams(1, 10, 3, 1, 64, 1, 0, {"persistent": 0, "megakernel": ctl.CTL_PT_MEGAKERNEL,
                                             "wavefront": ctl.CTL_PT_WAVEFRONT}[mode])
     want, wrays = oracle_render(orc, d, p, 3, 96, 64)

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 import oracle
-from helpers import binary_bvh, tie_rule
+from helpers import alpha_scene, binary_bvh, tie_rule
 
 pytestmark = pytest.mark.gpu
 
@@ -88,6 +88,18 @@ def test_all_draw_modes_bit_exact(ctl, orc, dev, mode, config, scale, w, h):
     assert same(wdep, gdep)
     if mode in (11, 14):
         assert grays > w * h                   # first_f_direct traces shadow rays
+
+
+@pytest.mark.parametrize("mode", ["first_f_direct", "uv"])
+def test_alpha_scene_bit_exact(ctl, orc, dev, mode):
+    """The alpha shading level of the prim kernel (no generated config has alpha
+    maps): primary and shadow rays pass through the cut-outs of helpers.alpha_scene."""
+    d, _ = alpha_scene(ctl)
+    mi = ctl._abi.PRIM_DRAW_MODES.index(mode)
+    got, gdep, grays = prim_gpu(ctl, d, mi, 5, dev, near=0.5, far=500.0)
+    want, wdep, wrays = prim_oracle(ctl, orc, d, mi, 5, near=0.5, far=500.0)
+    assert grays == wrays
+    assert same(want, got) and same(wdep, gdep)
 
 
 def test_prim_pass_rate(ctl, dev):
