@@ -88,7 +88,7 @@ constexpr uint32_t kMaxAnimations = 1u << 16;
 
 struct AnimMeshPlan {
     ctl_anim_mesh am;
-    std::vector<ResidentAnimation> resident;   // by animation index; freed with the state (allocs)
+    std::vector<ResidentAnimation> resident;   // by animation index; freed with the state (pool)
     ctl_kernel_mesh km;
     uint32_t n_entries = 0;
     uint32_t wide_base = 0;             // the mesh's first wide node
@@ -112,7 +112,7 @@ struct AnimState {
     float* d_mesh_boxes = nullptr;      // 6 per mesh
     float* d_inst_boxes = nullptr;      // 6 per node
     float* d_eps = nullptr;             // scene box (6) + eps + cull_m (3)
-    float* h_eps = nullptr;             // pinned: the same 10 floats, then 6 per node (instance boxes)
+    PinnedArray<float> h_eps;           // the same 10 floats, then 6 per node (instance boxes)
     float4* d_P = nullptr;
     float4* d_N = nullptr;
     size_t tmp_cap = 0;
@@ -121,7 +121,7 @@ struct AnimState {
     uint32_t n_meshes = 0, n_nodes = 0;
     std::vector<uint32_t> node_mesh;    // Node::m_uMeshIndex per node
     std::vector<uint32_t> node_lights;  // Node::m_uLights.size() per node
-    std::vector<void*> allocs;
+    DevPool pool;                       // owns the device arrays above and those of the meshes' plans
 };
 
 namespace {
@@ -731,11 +731,7 @@ __global__ void light_recalc_kernel(ctl_light* lights, uint32_t n_lights, ctl_li
 }
 
 template <class T>
-bool anim_alloc(AnimState* A, T** p, size_t n) {
-    if (hipMalloc((void**)p, n * sizeof(T) + 64) != hipSuccess) return false;
-    A->allocs.push_back((void*)*p);
-    return true;
-}
+bool anim_alloc(AnimState* A, T** p, size_t n) { return A->pool.alloc(p, n, 64) == hipSuccess; }
 
 template <class T>
 bool anim_upload(AnimState* A, T** dst, const T* src, size_t n) {
@@ -951,19 +947,19 @@ ctl_status scene_after_move(ctl_ctx* c, const std::vector<uint32_t>& moved, hipS
     hipLaunchKernelGGL(scene_eps_kernel, dim3(1), dim3(1), 0, s, A->d_inst_boxes, A->n_nodes, A->d_eps,
                        const_cast<ctl_env_light*>(S.env), A->d_mesh_boxes, A->n_meshes);
     if (hipGetLastError() != hipSuccess) { c->err = std::string(what) + ": launch failed"; return CTL_ERR_HIP; }
-    if (hipMemcpyAsync(A->h_eps, A->d_eps, 10 * sizeof(float), hipMemcpyDeviceToHost, s) != hipSuccess ||
-        hipMemcpyAsync(A->h_eps + 10, A->d_inst_boxes, 6 * sizeof(float) * A->n_nodes, hipMemcpyDeviceToHost, s) !=
+    if (hipMemcpyAsync(A->h_eps.get(), A->d_eps, 10 * sizeof(float), hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipMemcpyAsync(A->h_eps.get() + 10, A->d_inst_boxes, 6 * sizeof(float) * A->n_nodes, hipMemcpyDeviceToHost, s) !=
             hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess) {
         c->err = std::string(what) + ": readback failed";
         return CTL_ERR_HIP;
     }
-    if (!rebuild_scene(A, S, A->h_eps + 10, moved, s)) {
+    if (!rebuild_scene(A, S, A->h_eps.get() + 10, moved, s)) {
         c->err = std::string(what) + ": instance tree upload failed";
         return CTL_ERR_HIP;
     }
-    S.ray_eps = A->h_eps[6];
-    for (int k = 0; k < 3; k++) S.cull_m[k] = A->h_eps[7 + k];
+    S.ray_eps = A->h_eps.get()[6];
+    for (int k = 0; k < 3; k++) S.cull_m[k] = A->h_eps.get()[7 + k];
     c->device_eps = true;
     c->device_edited = true;
     return CTL_OK;
@@ -972,11 +968,7 @@ ctl_status scene_after_move(ctl_ctx* c, const std::vector<uint32_t>& moved, hipS
 }  // namespace
 
 void anim_free(ctl_ctx* c) {
-    AnimState* A = c->anim;
-    if (!A) return;
-    for (void* p : A->allocs) (void)hipFree(p);
-    if (A->h_eps) (void)hipHostFree(A->h_eps);
-    delete A;
+    delete c->anim;
     c->anim = nullptr;
 }
 
@@ -998,8 +990,7 @@ int anim_setup(ctl_ctx* c, const ctl_scene_desc* d, const std::vector<WideNode>&
     }
     if (!anim_upload(A, &A->d_mesh_boxes, d->mesh_boxes, 6ull * d->n_meshes) ||
         !anim_alloc(A, &A->d_inst_boxes, 6ull * std::max(1u, d->n_nodes)) || !anim_alloc(A, &A->d_eps, 10) ||
-        hipHostMalloc((void**)&A->h_eps, (10 + 6ull * std::max(1u, d->n_nodes)) * sizeof(float), hipHostMallocDefault) !=
-            hipSuccess)
+        A->h_eps.grow(10 + 6ull * std::max(1u, d->n_nodes)) != hipSuccess)
         return fail("animation state allocation failed");
     // the instance trees' host copies (ctl_scene_set_transform / animate rebuild them)
     if (d->n_nodes > 0 && d->scene_start_node >= 0 && d->n_scene_bvh_nodes > 0) {
@@ -1136,13 +1127,11 @@ CTL_API ctl_status ctl_scene_set_animation(ctl_ctx* c, uint32_t anim, uint32_t a
     if (hipDeviceSynchronize() != hipSuccess) { c->err = "scene_set_animation: sync failed"; return CTL_ERR_HIP; }
     if (!anim_alloc(A, &d, n)) { c->err = "scene_set_animation: frame table allocation failed"; return CTL_ERR_NOMEM; }
     if (hipMemcpy(d, frames, n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+        A->pool.release(d);
         c->err = "scene_set_animation: frame table upload failed";
         return CTL_ERR_HIP;
     }
-    if (R.d) {   // replaced: nothing in flight reads it after the synchronisation above
-        A->allocs.erase(std::remove(A->allocs.begin(), A->allocs.end(), (void*)R.d), A->allocs.end());
-        (void)hipFree(R.d);
-    }
+    if (R.d) A->pool.release(R.d);   // replaced: nothing in flight reads it after the synchronisation above
     R = ResidentAnimation{d, n_frames, n_bones};
     return CTL_OK;
 }
@@ -1385,22 +1374,20 @@ CTL_API ctl_status ctl_scene_array_size(ctl_ctx* c, uint32_t array, uint64_t* co
 static ctl_status grow_array(ctl_ctx* c, int a, uint64_t elems, size_t elem, size_t pad, uint64_t held) {
     SceneArray& A = c->sarr[a];
     const size_t need = (size_t)elems * elem + pad;
-    if (A.cap >= need) return CTL_OK;
-    void* p = nullptr;
+    if (A.mem.fits(need)) return CTL_OK;
+    DevArray<char> grown;
     if (hipDeviceSynchronize() != hipSuccess) { c->err = "scene_rebuild_mesh: device synchronisation failed"; return CTL_ERR_HIP; }
-    if (hipMalloc(&p, need) != hipSuccess) {
+    if (grown.grow(need) != hipSuccess) {
         c->err = "scene_rebuild_mesh: hipMalloc of " + std::to_string(need) + " bytes failed";
         return CTL_ERR_NOMEM;
     }
-    const size_t keep = std::min<size_t>((size_t)held * elem, A.cap);
-    if (hipMemset(p, 0, need) != hipSuccess || (keep && hipMemcpy(p, A.p, keep, hipMemcpyDeviceToDevice) != hipSuccess)) {
-        (void)hipFree(p);
+    const size_t keep = std::min<size_t>((size_t)held * elem, A.mem.cap());
+    if (hipMemset(grown.get(), 0, need) != hipSuccess ||
+        (keep && hipMemcpy(grown.get(), A.mem.get(), keep, hipMemcpyDeviceToDevice) != hipSuccess)) {
         c->err = "scene_rebuild_mesh: copy of the scene arrays failed";
         return CTL_ERR_HIP;
     }
-    if (A.p) (void)hipFree(A.p);
-    A.p = p;
-    A.cap = need;
+    A.mem = std::move(grown);
     return CTL_OK;
 }
 
@@ -1468,10 +1455,10 @@ CTL_API ctl_status ctl_scene_rebuild_mesh(ctl_ctx* c, uint32_t mesh, const float
             (r = grow_array(c, SA_IDX, up_entries + ee, sizeof(ctl_tri_index), sizeof(ctl_tri_index), up_entries + c->extra_entries + 1)) != CTL_OK ||
             (wide && (r = grow_array(c, SA_WBVH, up_wide + we, sizeof(WideNode), 0, up_wide + c->extra_wide)) != CTL_OK))
             return r;
-        S.bvh = reinterpret_cast<const float4*>(c->sarr[SA_BVH].p);
-        S.woop = reinterpret_cast<const float4*>(c->sarr[SA_WOOP].p);
-        S.tri_idx = reinterpret_cast<const uint32_t*>(c->sarr[SA_IDX].p);
-        if (wide) S.wbvh = reinterpret_cast<const float4*>(c->sarr[SA_WBVH].p);
+        S.bvh = reinterpret_cast<const float4*>(c->sarr[SA_BVH].mem.get());
+        S.woop = reinterpret_cast<const float4*>(c->sarr[SA_WOOP].mem.get());
+        S.tri_idx = reinterpret_cast<const uint32_t*>(c->sarr[SA_IDX].mem.get());
+        if (wide) S.wbvh = reinterpret_cast<const float4*>(c->sarr[SA_WBVH].mem.get());
         c->extra_nodes = ne;
         c->extra_entries = ee;
         if (wide) c->extra_wide = we;
@@ -1484,10 +1471,10 @@ CTL_API ctl_status ctl_scene_rebuild_mesh(ctl_ctx* c, uint32_t mesh, const float
     }
     const int t = G.cur == 0 ? 1 : 0;   // the region the mesh is not using
     const auto clk0 = std::chrono::steady_clock::now();
-    float* nodes = reinterpret_cast<float*>(c->sarr[SA_BVH].p) + 16 * G.node0[t];
-    float* woop = reinterpret_cast<float*>(c->sarr[SA_WOOP].p) + 12 * G.entry0[t];
-    uint32_t* idx = reinterpret_cast<uint32_t*>(c->sarr[SA_IDX].p) + G.entry0[t];
-    WideNode* wn = wide ? reinterpret_cast<WideNode*>(c->sarr[SA_WBVH].p) + G.wide0[t] : nullptr;
+    float* nodes = reinterpret_cast<float*>(c->sarr[SA_BVH].mem.get()) + 16 * G.node0[t];
+    float* woop = reinterpret_cast<float*>(c->sarr[SA_WOOP].mem.get()) + 12 * G.entry0[t];
+    uint32_t* idx = reinterpret_cast<uint32_t*>(c->sarr[SA_IDX].mem.get()) + G.entry0[t];
+    WideNode* wn = wide ? reinterpret_cast<WideNode*>(c->sarr[SA_WBVH].mem.get()) + G.wide0[t] : nullptr;
     ctl_status r = (ctl_status)lbvh_build(c, d_positions, n_tris, nodes, woop, idx, wn, s);
     if (r != CTL_OK) return r;
     if (hipStreamSynchronize(s) != hipSuccess) { c->err = "scene_rebuild_mesh: build failed"; return CTL_ERR_HIP; }

@@ -21,6 +21,8 @@
 #include <algorithm>
 #include <cstdint>
 
+#include "devmem.h"
+
 namespace {
 
 constexpr int kBlock = 256;
@@ -80,8 +82,8 @@ struct Dev {
 // best and mean of `reps` timed launches (after one warm-up); -1 on a HIP error
 template <class F>
 int time_reps(int reps, F launch, float* best_ms, float* mean_ms) {
-    hipEvent_t e0, e1;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return -1;
+    ctl::Event e0, e1;
+    if (e0.create() != hipSuccess || e1.create() != hipSuccess) return -1;
     launch();
     if (hipDeviceSynchronize() != hipSuccess) return -1;
     float best = 1e30f, sum = 0.0f;
@@ -95,8 +97,6 @@ int time_reps(int reps, F launch, float* best_ms, float* mean_ms) {
         best = std::min(best, ms);
         sum += ms;
     }
-    hipEventDestroy(e0);
-    hipEventDestroy(e1);
     *best_ms = best;
     *mean_ms = sum / reps;
     return hipGetLastError() == hipSuccess ? 0 : -1;
@@ -112,19 +112,17 @@ __attribute__((visibility("default"))) int ctl_ceiling_hbm_read(int device, uint
     if (!out || bytes < (1u << 20) || reps < 1) return -1;
     Dev g(device);
     const uint64_t n = bytes / 16;
-    uint4* p = nullptr;
-    uint32_t* o = nullptr;
-    if (hipMalloc(&p, n * 16) != hipSuccess) return -1;
-    if (hipMalloc(&o, 4) != hipSuccess) { hipFree(p); return -1; }
+    ctl::DevArray<uint4> nodes;
+    ctl::DevArray<uint32_t> sink;
+    if (nodes.grow(n) != hipSuccess || sink.grow(1) != hipSuccess) return -1;
+    uint4* const p = nodes.get();
     int cus = 0;
     hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
     const int blocks = std::max(1, cus) * 8;   // 8 blocks of 4 waves per CU
     hipLaunchKernelGGL(fill_kernel, dim3(blocks), dim3(kBlock), 0, 0, p, n, 0x5EEDu);
     float best = 0, mean = 0;
-    const int r = time_reps(reps, [&] { hipLaunchKernelGGL(hbm_read_kernel, dim3(blocks), dim3(kBlock), 0, 0, p, n, o); },
+    const int r = time_reps(reps, [&] { hipLaunchKernelGGL(hbm_read_kernel, dim3(blocks), dim3(kBlock), 0, 0, p, n, sink.get()); },
                             &best, &mean);
-    hipFree(p);
-    hipFree(o);
     if (r) return -1;
     out[0] = (double)(n * 16) / (best * 1e-3) / 1e9;
     out[1] = (double)(n * 16) / (mean * 1e-3) / 1e9;
@@ -148,10 +146,10 @@ __attribute__((visibility("default"))) int ctl_ceiling_node_chain(int device, ui
     while (n_nodes64 * 2 <= bytes / 128) n_nodes64 *= 2;
     if (n_nodes64 > 0x80000000ull) return -1;
     const uint32_t n_nodes = (uint32_t)n_nodes64;
-    uint4* p = nullptr;
-    uint32_t* o = nullptr;
-    if (hipMalloc(&p, (size_t)n_nodes * 128) != hipSuccess) return -1;
-    if (hipMalloc(&o, 4) != hipSuccess) { hipFree(p); return -1; }
+    ctl::DevArray<uint4> nodes;
+    ctl::DevArray<uint32_t> sink;
+    if (nodes.grow((size_t)n_nodes * 8) != hipSuccess || sink.grow(1) != hipSuccess) return -1;
+    uint4* const p = nodes.get();
     int cus = 0;
     hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
     cus = std::max(1, cus);
@@ -161,10 +159,8 @@ __attribute__((visibility("default"))) int ctl_ceiling_node_chain(int device, ui
     float best = 0, mean = 0;
     const int r = time_reps(reps, [&] {
         hipLaunchKernelGGL(node_chain_kernel, dim3(blocks), dim3(kBlock), 0, 0, p, n_nodes - 1, steps, active, share,
-                           o);
+                           sink.get());
     }, &best, &mean);
-    hipFree(p);
-    hipFree(o);
     if (r) return -1;
     const double lane_steps = (double)blocks * 4.0 * active * steps;
     out[0] = lane_steps / (best * 1e-3);

@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 
+#include "devmem.h"
 #include "dispatch.h"
 #include "traverse.h"
 #include "../ctl_env.h"
@@ -736,9 +737,8 @@ enum SceneArr : int {
     SA_COUNT
 };
 struct SceneArray {
-    void* p = nullptr;
-    size_t bytes = 0;   // bytes of the current contents
-    size_t cap = 0;     // allocated
+    DevArray<char> mem;   // cap(): bytes allocated
+    size_t bytes = 0;     // bytes of the current contents
 };
 
 }  // namespace ctl
@@ -759,47 +759,43 @@ struct ctl_ctx {
     bool half_quirk = false;
     bool has_delta = false;                     // some uploaded material has a delta lobe (prim.hip)
     uint32_t nseq = 4096, len = 30;
-    float* d_s1[2] = {nullptr, nullptr};
-    float2* d_s2[2] = {nullptr, nullptr};
+    ctl::DevPool fixed;                         // owns the arrays allocated once by ctl_create
+    float* d_s1[2] = {nullptr, nullptr};        // (fixed)
+    float2* d_s2[2] = {nullptr, nullptr};       // (fixed)
     // ctl_render_passes: sampler tables of every pass of one launch, and the
     // per-pass sample slices of the owned tiles (folded into the caller's
     // framebuffer in pass order)
-    float* d_mt1 = nullptr;
-    float2* d_mt2 = nullptr;
-    uint32_t mt_cap = 0;        // tables allocated
-    float4* d_slices = nullptr; // SampleSlots of the path kernels (common.h)
-    uint64_t slices_cap = 0;    // float4 elements allocated
-    float* h_s1[2] = {nullptr, nullptr};
-    float* h_s2[2] = {nullptr, nullptr};
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    ctl::DevArray<float> d_mt1;
+    ctl::DevArray<float2> d_mt2;
+    ctl::DevArray<float4> d_slices;             // SampleSlots of the path kernels (common.h)
+    ctl::PinnedArray<float> h_s1[2], h_s2[2];
+    ctl::Event ev[2];
     int next_buf = 0, active = -1;
-    unsigned long long* d_counters = nullptr;   // [0] rays [1] overflow [2..4] stats
-    unsigned long long* h_overflow = nullptr;   // pinned host copy of d_counters[1], read at ctl_sync
+    unsigned long long* d_counters = nullptr;   // [0] rays [1] overflow [2..4] stats (fixed)
+    ctl::PinnedArray<unsigned long long> h_overflow;   // host copy of d_counters[1], read at ctl_sync
     bool overflow_seen = false;                 // sticky: a traversal stack overflowed since the last reset
     // 64-bit work cursors ([0] batch intersect [1] path pass [2] prim pass): resident
     // lanes fetch once more after the work runs out, which a 32-bit cursor
     // near 2^32 items would wrap
-    unsigned long long* d_cursors = nullptr;
+    unsigned long long* d_cursors = nullptr;    // (fixed)
     std::vector<std::pair<const void*, std::pair<size_t, int>>> resident;   // resident_blocks cache
-    hipEvent_t pass_ev[2] = {nullptr, nullptr}; // bracket the last render pass (ctl_last_pass_ms)
+    ctl::Event pass_ev[2];                      // bracket the last render pass (ctl_last_pass_ms)
     bool pass_timed = false;
     size_t wide_nodes = 0;
     int stack_bound = 0;                        // worst-case traversal stack of the uploaded scene
-    uint8_t* d_tile_flags = nullptr;            // PixelVarianceBuffer block flags
-    size_t tile_flags_cap = 0;
+    ctl::DevArray<uint8_t> d_tile_flags;        // PixelVarianceBuffer block flags
     // ctl_render_pass_blocks: the OwnList tables (OwnList::words), filled in one half
     // of the pinned staging buffer and uploaded stream-ordered.  The halves alternate
     // and block_ev[h] marks half h's last upload, so the host waits only for the
     // upload of two calls ago and a caller can queue list passes without stalling.
-    uint32_t* d_block_tbl = nullptr;
-    uint32_t* h_block_tbl = nullptr;            // 2 x OwnList::words(block_tbl_cap)
-    size_t block_tbl_cap = 0;                   // tiles the copies are allocated for
-    hipEvent_t block_ev[2] = {nullptr, nullptr};
+    ctl::DevArray<uint32_t> d_block_tbl;        // OwnList::words(tiles allocated for)
+    ctl::PinnedArray<uint32_t> h_block_tbl;     // two halves of d_block_tbl.cap() words
+    ctl::Event block_ev[2];
     bool block_ev_set[2] = {false, false};      // block_ev[h] has been recorded
     uint32_t block_half = 0;                    // the half the next call fills
-    uint32_t* d_powers = nullptr;               // XORWOW step powers for sampler_kernel
+    uint32_t* d_powers = nullptr;               // XORWOW step powers for sampler_kernel (fixed)
     ctl::WfState wf{};
-    std::vector<void*> wf_allocs;
+    ctl::DevPool wf_pool;                       // owns wf's arrays
     ctl::WptBuffers* wpt = nullptr;             // WavefrontPathTracer queues (wpt.hip)
     ctl::AnimState* anim = nullptr;             // animated meshes, refit plans (anim.hip)
     ctl::ImageState* img = nullptr;             // image pipeline scratch and NLM weights (pipeline.hip)
@@ -878,7 +874,6 @@ dim3 resident_grid(ctl_ctx* c, K kernel, size_t lds, uint64_t want, int bpc = 0)
 void free_scene(ctl_ctx* c);
 // wavefront.hip
 int wavefront_pass(ctl_ctx* c, const PathParams& P, const SampleSlots& SS, bool stats, hipStream_t s);
-void wavefront_free(ctl_ctx* c);
 // anim.hip
 struct WideNode;
 int anim_setup(ctl_ctx* c, const ctl_scene_desc* d, const std::vector<WideNode>& wn, const std::vector<uint32_t>& wbase,

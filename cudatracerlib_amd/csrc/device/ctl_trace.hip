@@ -552,7 +552,9 @@ CTL_API const char* ctl_last_error(const ctl_ctx* ctx) {
 }
 
 CTL_API ctl_ctx* ctl_create(int32_t device) {
-    auto fail = [](const std::string& s) -> ctl_ctx* {
+    ctl_ctx* c = nullptr;
+    auto fail = [&c](const std::string& s) -> ctl_ctx* {
+        ctl_destroy(c);   // frees what the context already owns
         std::lock_guard<std::mutex> g(g_err_mtx);
         g_create_err = s;
         return nullptr;
@@ -565,75 +567,44 @@ CTL_API ctl_ctx* ctl_create(int32_t device) {
     if (hipGetDeviceProperties(&prop, device) != hipSuccess) return fail("ctl_create: hipGetDeviceProperties failed");
     if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
         return fail(std::string("ctl_create: device is ") + prop.gcnArchName + ", kernels are built for gfx950 only");
-    ctl_ctx* c = new ctl_ctx();
+    c = new ctl_ctx();
     c->device = device;
     c->cu_count = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    if (hipMalloc(&c->d_counters, 16 * sizeof(unsigned long long)) != hipSuccess ||
-        hipMemset(c->d_counters, 0, 16 * sizeof(unsigned long long)) != hipSuccess) {
-        delete c;
+    if (c->fixed.alloc(&c->d_counters, 16) != hipSuccess ||
+        hipMemset(c->d_counters, 0, 16 * sizeof(unsigned long long)) != hipSuccess)
         return fail("ctl_create: counter allocation failed");
-    }
-    if (hipMalloc(&c->d_cursors, 16 * sizeof(unsigned long long)) != hipSuccess ||
+    if (c->fixed.alloc(&c->d_cursors, 16) != hipSuccess ||
         hipMemset(c->d_cursors, 0, 16 * sizeof(unsigned long long)) != hipSuccess ||
-        hipHostMalloc(&c->h_overflow, sizeof(unsigned long long)) != hipSuccess ||
-        hipEventCreate(&c->pass_ev[0]) != hipSuccess || hipEventCreate(&c->pass_ev[1]) != hipSuccess) {
-        ctl_destroy(c);
+        c->h_overflow.grow(1) != hipSuccess ||
+        c->pass_ev[0].create() != hipSuccess || c->pass_ev[1].create() != hipSuccess)
         return fail("ctl_create: cursor/event allocation failed");
-    }
     {
         std::vector<uint32_t> pw((size_t)kJumpBits * 800 + 130 * 800);
         ctl::sampler_step_powers(pw.data(), kJumpBits);
         ctl::sampler_seq_powers(pw.data() + kSeqPowBase, c->len);
-        if (hipMalloc(&c->d_powers, pw.size() * 4) != hipSuccess ||
-            hipMemcpy(c->d_powers, pw.data(), pw.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-            ctl_destroy(c);
+        if (c->fixed.alloc(&c->d_powers, pw.size()) != hipSuccess ||
+            hipMemcpy(c->d_powers, pw.data(), pw.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
             return fail("ctl_create: sampler power table allocation failed");
-        }
     }
     for (int i = 0; i < 2; i++) {
         size_t n1 = (size_t)c->nseq * c->len;
-        if (hipMalloc(&c->d_s1[i], n1 * sizeof(float)) != hipSuccess ||
-            hipMalloc(&c->d_s2[i], n1 * sizeof(float2)) != hipSuccess ||
-            hipHostMalloc(&c->h_s1[i], n1 * sizeof(float)) != hipSuccess ||
-            hipHostMalloc(&c->h_s2[i], n1 * 2 * sizeof(float)) != hipSuccess ||
-            hipEventCreateWithFlags(&c->ev[i], hipEventDisableTiming) != hipSuccess) {
-            ctl_destroy(c);
+        if (c->fixed.alloc(&c->d_s1[i], n1) != hipSuccess || c->fixed.alloc(&c->d_s2[i], n1) != hipSuccess ||
+            c->h_s1[i].grow(n1) != hipSuccess || c->h_s2[i].grow(n1 * 2) != hipSuccess ||
+            c->ev[i].create(hipEventDisableTiming) != hipSuccess)
             return fail("ctl_create: sampler buffer allocation failed");
-        }
     }
     return c;
 }
 
+// The context's own buffers and events go with their owners (devmem.h).
 CTL_API void ctl_destroy(ctl_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
     free_scene(c);
-    ctl::wavefront_free(c);
     ctl::wpt_free(c);
     ctl::anim_free(c);
     ctl::image_free(c);
-    if (c->d_mt1) (void)hipFree(c->d_mt1);
-    if (c->d_mt2) (void)hipFree(c->d_mt2);
-    if (c->d_slices) (void)hipFree(c->d_slices);
-    for (int i = 0; i < 2; i++) {
-        if (c->d_s1[i]) (void)hipFree(c->d_s1[i]);
-        if (c->d_s2[i]) (void)hipFree(c->d_s2[i]);
-        if (c->h_s1[i]) (void)hipHostFree(c->h_s1[i]);
-        if (c->h_s2[i]) (void)hipHostFree(c->h_s2[i]);
-        if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
-    }
-    if (c->d_counters) (void)hipFree(c->d_counters);
-    if (c->d_cursors) (void)hipFree(c->d_cursors);
-    if (c->h_overflow) (void)hipHostFree(c->h_overflow);
-    if (c->d_tile_flags) (void)hipFree(c->d_tile_flags);
-    if (c->d_block_tbl) (void)hipFree(c->d_block_tbl);
-    if (c->h_block_tbl) (void)hipHostFree(c->h_block_tbl);
-    for (int i = 0; i < 2; i++)
-        if (c->block_ev[i]) (void)hipEventDestroy(c->block_ev[i]);
-    for (int i = 0; i < 2; i++)
-        if (c->pass_ev[i]) (void)hipEventDestroy(c->pass_ev[i]);
-    if (c->d_powers) (void)hipFree(c->d_powers);
     delete c;
 }
 
@@ -646,10 +617,10 @@ CTL_API ctl_status ctl_sampler_upload(ctl_ctx* c, const float* seq1d, const floa
     int b = c->next_buf;
     size_t n1 = (size_t)nseq * len;
     CTL_HIP(c, hipEventSynchronize(c->ev[b]));
-    std::memcpy(c->h_s1[b], seq1d, n1 * sizeof(float));
-    std::memcpy(c->h_s2[b], seq2d, n1 * 2 * sizeof(float));
-    CTL_HIP(c, hipMemcpyAsync(c->d_s1[b], c->h_s1[b], n1 * sizeof(float), hipMemcpyHostToDevice, s));
-    CTL_HIP(c, hipMemcpyAsync(c->d_s2[b], c->h_s2[b], n1 * 2 * sizeof(float), hipMemcpyHostToDevice, s));
+    std::memcpy(c->h_s1[b].get(), seq1d, n1 * sizeof(float));
+    std::memcpy(c->h_s2[b].get(), seq2d, n1 * 2 * sizeof(float));
+    CTL_HIP(c, hipMemcpyAsync(c->d_s1[b], c->h_s1[b].get(), n1 * sizeof(float), hipMemcpyHostToDevice, s));
+    CTL_HIP(c, hipMemcpyAsync(c->d_s2[b], c->h_s2[b].get(), n1 * 2 * sizeof(float), hipMemcpyHostToDevice, s));
     CTL_HIP(c, hipEventRecord(c->ev[b], s));
     c->active = b;
     c->next_buf = 1 - b;
@@ -806,7 +777,7 @@ static ctl_status launch_pass(ctl_ctx* c, const ctl_pt_params* p, ctl_pixel* fb,
     ctl_status r1 = prepare_slots(c, threads, s);   // every schedule stores samples per work item
     if (r1 != CTL_OK) return r1;
     ctl_status r2 = launch_schedule(c, p, P, fb, stats, s, threads, grid, s1, s2,
-                                    make_slots(c->d_slices, (uint32_t)threads), 0);
+                                    make_slots(c->d_slices.get(), (uint32_t)threads), 0);
     if (r2 != CTL_OK) return r2;
     launch_fold(c, P, (uint32_t)threads, 1, fb, s, 0);
     CTL_HIP(c, hipEventRecord(c->pass_ev[1], s));
@@ -898,15 +869,12 @@ __global__ __launch_bounds__(kBlock) void fold_samples_kernel(PathParams P, cons
 // drop the sample), so no clearing is needed.
 static ctl_status prepare_slots(ctl_ctx* c, uint64_t items, hipStream_t s) {
     c->spec.pending = false;   // the slots are about to be overwritten
-    if (c->slices_cap < items) {
+    if (!c->d_slices.fits(items)) {
         CTL_HIP(c, hipStreamSynchronize(s));
-        if (c->d_slices) (void)hipFree(c->d_slices);
-        c->d_slices = nullptr; c->slices_cap = 0;
-        if (hipMalloc(&c->d_slices, items * sizeof(float4)) != hipSuccess) {
+        if (c->d_slices.grow(items) != hipSuccess) {
             c->err = "render_pass: sample slot allocation failed";
             return CTL_ERR_NOMEM;
         }
-        c->slices_cap = items;
     }
     return CTL_OK;
 }
@@ -915,7 +883,7 @@ static void launch_fold(ctl_ctx* c, const PathParams& P, uint32_t per_pass, uint
                         uint32_t first_slice = 0) {
     const uint64_t px = (uint64_t)P.width * P.height;
     hipLaunchKernelGGL(fold_samples_kernel, dim3((unsigned)((px + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, P,
-                       c->d_slices + (size_t)first_slice * per_pass, per_pass, n, fb);
+                       c->d_slices.get() + (size_t)first_slice * per_pass, per_pass, n, fb);
 }
 
 // n_passes consecutive passes in one persistent launch; the first n_fold of them
@@ -953,17 +921,14 @@ static ctl_status launch_window(ctl_ctx* c, const ctl_pt_params* params, uint64_
     const uint64_t items = per_pass * n_passes;
     if (items >= 0xffffffffull) { c->err = "render_passes: 2^32-1 or more work items"; return CTL_ERR_INVALID; }
     const size_t tbl = (size_t)c->nseq * c->len;
-    if (c->mt_cap < n_passes) {
+    if (!c->d_mt1.fits(tbl * n_passes) || !c->d_mt2.fits(tbl * n_passes)) {
         CTL_HIP(c, hipStreamSynchronize(s));
-        if (c->d_mt1) (void)hipFree(c->d_mt1);
-        if (c->d_mt2) (void)hipFree(c->d_mt2);
-        c->d_mt1 = nullptr; c->d_mt2 = nullptr; c->mt_cap = 0;
-        if (hipMalloc(&c->d_mt1, tbl * n_passes * sizeof(float)) != hipSuccess ||
-            hipMalloc(&c->d_mt2, tbl * n_passes * sizeof(float2)) != hipSuccess) {
+        c->d_mt1.reset();
+        c->d_mt2.reset();
+        if (c->d_mt1.grow(tbl * n_passes) != hipSuccess || c->d_mt2.grow(tbl * n_passes) != hipSuccess) {
             c->err = "render_passes: sampler table allocation failed";
             return CTL_ERR_NOMEM;
         }
-        c->mt_cap = n_passes;
     }
     CTL_HIP(c, hipEventRecord(c->pass_ev[0], s));
     for (uint32_t i0 = 0; i0 < n_passes; i0 += kSamplerBatch) {
@@ -972,12 +937,12 @@ static ctl_status launch_window(ctl_ctx* c, const ctl_pt_params* params, uint64_
         for (uint32_t i = 0; i < nb; i++)
             ctl::sampler_pass_state(first_pass + i0 + i, c->nseq, c->len, B.b[i].v, &B.b[i].d);
         hipLaunchKernelGGL(sampler_batch_kernel, dim3((c->nseq + 3) / 4, nb), dim3(256), 0, s, c->d_powers, B, c->nseq,
-                           c->len, c->d_mt1 + i0 * tbl, c->d_mt2 + i0 * tbl, (uint64_t)tbl);
+                           c->len, c->d_mt1.get() + i0 * tbl, c->d_mt2.get() + i0 * tbl, (uint64_t)tbl);
     }
     r = prepare_slots(c, items, s);
     if (r != CTL_OK) return r;
-    r = launch_schedule(c, params, P, d_fb, false, s, items, dim3(1), c->d_mt1, c->d_mt2,
-                        make_slots(c->d_slices, (uint32_t)per_pass), (uint32_t)tbl);
+    r = launch_schedule(c, params, P, d_fb, false, s, items, dim3(1), c->d_mt1.get(), c->d_mt2.get(),
+                        make_slots(c->d_slices.get(), (uint32_t)per_pass), (uint32_t)tbl);
     if (r != CTL_OK) return r;
     launch_fold(c, P, (uint32_t)per_pass, n_fold, d_fb, s, 0);
     CTL_HIP(c, hipGetLastError());
@@ -1131,28 +1096,27 @@ CTL_API ctl_status ctl_render_pass_blocks(ctl_ctx* c, const ctl_pt_params* p, co
     CTL_HIP(c, hipSetDevice(c->device));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const uint32_t nt = P.num_tiles, ts = P.tile_size;
-    if (c->block_tbl_cap < nt) {
+    if (!c->d_block_tbl.fits(OwnList::words(nt)) || !c->h_block_tbl.fits(2 * OwnList::words(nt))) {
         for (int i = 0; i < 2; i++) {
             if (c->block_ev_set[i]) CTL_HIP(c, hipEventSynchronize(c->block_ev[i]));
             c->block_ev_set[i] = false;
-            if (!c->block_ev[i]) CTL_HIP(c, hipEventCreateWithFlags(&c->block_ev[i], hipEventDisableTiming));
+            if (!c->block_ev[i])
+                CTL_HIP_AS(c, c->block_ev[i].create(hipEventDisableTiming), "hipEventCreateWithFlags");
         }
         CTL_HIP(c, hipStreamSynchronize(s));
-        if (c->d_block_tbl) (void)hipFree(c->d_block_tbl);
-        if (c->h_block_tbl) (void)hipHostFree(c->h_block_tbl);
-        c->d_block_tbl = nullptr; c->h_block_tbl = nullptr; c->block_tbl_cap = 0;
-        if (hipMalloc(&c->d_block_tbl, OwnList::words(nt) * sizeof(uint32_t)) != hipSuccess ||
-            hipHostMalloc(&c->h_block_tbl, 2 * OwnList::words(nt) * sizeof(uint32_t)) != hipSuccess) {
+        c->d_block_tbl.reset();
+        c->h_block_tbl.reset();
+        if (c->d_block_tbl.grow(OwnList::words(nt)) != hipSuccess ||
+            c->h_block_tbl.grow(2 * OwnList::words(nt)) != hipSuccess) {
             c->err = "render_pass_blocks: block table allocation failed";
             return CTL_ERR_NOMEM;
         }
-        c->block_tbl_cap = nt;
     }
     // the staging half of two calls ago: its upload has usually long left it
     const uint32_t half = c->block_half;
     if (c->block_ev_set[half]) CTL_HIP(c, hipEventSynchronize(c->block_ev[half]));
     // OwnList tables (common.h): slots in order of first appearance in the list
-    uint32_t* origin = c->h_block_tbl + half * OwnList::words(c->block_tbl_cap);
+    uint32_t* origin = c->h_block_tbl.get() + half * c->d_block_tbl.cap();
     uint32_t* slot_of = origin + OwnList::slot_of_off(nt);
     uint32_t* mult = origin + OwnList::mult_off(nt);
     std::fill(origin, origin + 2 * (size_t)nt, 0u);
@@ -1180,7 +1144,8 @@ CTL_API ctl_status ctl_render_pass_blocks(ctl_ctx* c, const ctl_pt_params* p, co
     if (items > kListItemMask) { c->err = "render_pass_blocks: 2^29 or more work items"; return CTL_ERR_INVALID; }
     P.owned_items = (uint32_t)own;
     CTL_HIP(c, hipEventRecord(c->pass_ev[0], s));
-    CTL_HIP(c, hipMemcpyAsync(c->d_block_tbl, origin, OwnList::words(nt) * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    CTL_HIP(c, hipMemcpyAsync(c->d_block_tbl.get(), origin, OwnList::words(nt) * sizeof(uint32_t), hipMemcpyHostToDevice,
+                              s));
     CTL_HIP(c, hipEventRecord(c->block_ev[half], s));
     c->block_ev_set[half] = true;
     c->block_half = half ^ 1;
@@ -1189,7 +1154,7 @@ CTL_API ctl_status ctl_render_pass_blocks(ctl_ctx* c, const ctl_pt_params* p, co
     unsigned long long* cursor = c->d_cursors + 1;
     CTL_HIP(c, hipMemsetAsync(cursor, 0, sizeof(unsigned long long), s));
     const uint64_t want = (items + kBlock - 1) / kBlock;
-    const SampleSlots PS = make_slots(c->d_slices, (uint32_t)items);
+    const SampleSlots PS = make_slots(c->d_slices.get(), (uint32_t)items);
     const float* s1 = c->d_s1[c->active];
     const float2* s2 = c->d_s2[c->active];
     with_tree(c->scene.single != 0, c->scene.wide != 0, [&](auto SG, auto WD) {
@@ -1197,12 +1162,12 @@ CTL_API ctl_status ctl_render_pass_blocks(ctl_ctx* c, const ctl_pt_params* p, co
             constexpr size_t lds = persistent_lds_bytes();
             auto k = path_kernel_persistent_blocks<decltype(SG)::value, decltype(WD)::value, decltype(FU)::value>;
             hipLaunchKernelGGL(k, resident_grid(c, k, lds, want, CTL_PERSIST_BPC), dim3(kBlock), lds, s, c->scene, P,
-                               s1, s2, items, cursor, c->d_counters, PS, (const uint32_t*)c->d_block_tbl);
+                               s1, s2, items, cursor, c->d_counters, PS, (const uint32_t*)c->d_block_tbl.get());
         });
     });
     CTL_HIP(c, hipGetLastError());
     hipLaunchKernelGGL(fold_blocks_kernel, dim3((unsigned)((own + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, P,
-                       (const uint32_t*)c->d_block_tbl, (const float4*)c->d_slices, d_fb);
+                       (const uint32_t*)c->d_block_tbl.get(), (const float4*)c->d_slices.get(), d_fb);
     CTL_HIP(c, hipGetLastError());
     CTL_HIP(c, hipEventRecord(c->pass_ev[1], s));
     c->pass_timed = true;
@@ -1290,9 +1255,10 @@ CTL_API ctl_status ctl_sync(ctl_ctx* c, void* stream) {
     if (!c) return CTL_ERR_INVALID;
     CTL_HIP(c, hipSetDevice(c->device));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    CTL_HIP(c, hipMemcpyAsync(c->h_overflow, c->d_counters + 1, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    CTL_HIP(c, hipMemcpyAsync(c->h_overflow.get(), c->d_counters + 1, sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                              s));
     CTL_HIP(c, hipStreamSynchronize(s));
-    note_overflow(c, *c->h_overflow);
+    note_overflow(c, *c->h_overflow.get());
     return c->overflow_seen ? CTL_ERR_STATE : CTL_OK;
 }
 

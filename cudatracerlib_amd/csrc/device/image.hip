@@ -170,20 +170,16 @@ CTL_API ctl_status ctl_variance_add_pass(ctl_ctx* c, const ctl_pixel* fb, uint32
     const uint32_t tx = (w + tile - 1) / tile, ty = (h + tile - 1) / tile;
     CTL_HIP(c, hipSetDevice(c->device));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (c->tile_flags_cap < (size_t)tx * ty) {
+    if (!c->d_tile_flags.fits((size_t)tx * ty)) {
         CTL_HIP(c, hipStreamSynchronize(s));
-        if (c->d_tile_flags) (void)hipFree(c->d_tile_flags);
-        c->d_tile_flags = nullptr;
-        c->tile_flags_cap = 0;
-        CTL_HIP(c, hipMalloc(&c->d_tile_flags, (size_t)tx * ty));
-        c->tile_flags_cap = (size_t)tx * ty;
+        CTL_HIP_AS(c, c->d_tile_flags.grow((size_t)tx * ty), "variance_add_pass: block flag allocation");
     }
     // pageable source: the copy completes before the call returns, so the
     // caller may reuse tile_samples immediately
-    CTL_HIP(c, hipMemcpyAsync(c->d_tile_flags, tile_samples, (size_t)tx * ty, hipMemcpyHostToDevice, s));
+    CTL_HIP(c, hipMemcpyAsync(c->d_tile_flags.get(), tile_samples, (size_t)tx * ty, hipMemcpyHostToDevice, s));
     CTL_HIP(c, hipStreamSynchronize(s));
     hipLaunchKernelGGL(variance_add_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, fb, w, h,
-                       splat, tile, tx, c->d_tile_flags, var);
+                       splat, tile, tx, c->d_tile_flags.get(), var);
     CTL_HIP(c, hipGetLastError());
     return CTL_OK;
 }

@@ -66,7 +66,7 @@
 namespace ctl {
 
 struct LbvhScratch {
-    uint32_t cap = 0;               // triangles the arrays are sized for
+    uint32_t cap = 0;               // triangles the arrays are sized for (0: the pointers below are not valid)
     uint64_t* keys[2] = {nullptr, nullptr};
     uint32_t* vals[2] = {nullptr, nullptr};
     uint32_t* lpar = nullptr;       // per entry: its parent node
@@ -78,10 +78,11 @@ struct LbvhScratch {
     uint32_t* flag = nullptr;       // per inner node: starts a wide node
     uint32_t* widx = nullptr;       // exclusive prefix sum of flag
     int4* wkids = nullptr;          // per wide-node start: its slots' binary child words
-    uint32_t* d_res = nullptr;      // kLbvhResWords words (LbvhRes)
-    uint32_t* h_res = nullptr;      // pinned copy
-    void* tmp = nullptr;            // rocPRIM temporary storage
+    char* tmp = nullptr;            // rocPRIM temporary storage
     size_t tmp_bytes = 0;
+    DevPool pool;                   // owns the arrays above
+    DevArray<uint32_t> d_res;       // kLbvhResWords words (LbvhRes), then the level counts; kept across a regrow
+    PinnedArray<uint32_t> h_res;    // copy of the result words
 };
 
 namespace {
@@ -481,30 +482,17 @@ __global__ void lbvh_single_kernel(const float* __restrict__ pos, float* nodes, 
 }
 
 template <class T>
-bool scratch_alloc(T** p, size_t n) {
-    return hipMalloc((void**)p, std::max<size_t>(n, 1) * sizeof(T)) == hipSuccess;
-}
+bool scratch_alloc(LbvhScratch* L, T** p, size_t n) { return L->pool.alloc(p, std::max<size_t>(n, 1)) == hipSuccess; }
 
 void scratch_release(LbvhScratch* L) {
-    void* ps[] = {L->keys[0], L->keys[1], L->vals[0], L->vals[1], L->lpar, L->lbox, L->nbox, L->cnt,
-                  L->front, L->below, L->flag, L->widx, L->wkids, L->tmp};
-    for (void* p : ps)
-        if (p) (void)hipFree(p);
-    const LbvhScratch keep = *L;
-    *L = LbvhScratch{};
-    L->d_res = keep.d_res;
-    L->h_res = keep.h_res;
+    L->pool.clear();
+    L->cap = 0;
 }
 
 }  // namespace
 
 void lbvh_free(ctl_ctx* c) {
-    LbvhScratch* L = c->lbvh;
-    if (!L) return;
-    scratch_release(L);
-    if (L->d_res) (void)hipFree(L->d_res);
-    if (L->h_res) (void)hipHostFree(L->h_res);
-    delete L;
+    delete c->lbvh;
     c->lbvh = nullptr;
 }
 
@@ -513,9 +501,8 @@ void lbvh_free(ctl_ctx* c) {
 int lbvh_reserve(ctl_ctx* c, uint32_t n) {
     if (!c->lbvh) c->lbvh = new LbvhScratch();
     LbvhScratch* L = c->lbvh;
-    if (!L->d_res) {
-        if (hipMalloc((void**)&L->d_res, (kLbvhResWords + kLevelWords) * sizeof(uint32_t)) != hipSuccess ||
-            hipHostMalloc((void**)&L->h_res, kLbvhResWords * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess) {
+    if (!L->d_res || !L->h_res) {
+        if (L->d_res.grow(kLbvhResWords + kLevelWords) != hipSuccess || L->h_res.grow(kLbvhResWords) != hipSuccess) {
             c->err = "scene_rebuild_mesh: scratch allocation failed";
             return CTL_ERR_NOMEM;
         }
@@ -532,11 +519,12 @@ int lbvh_reserve(ctl_ctx* c, uint32_t n) {
         return CTL_ERR_HIP;
     }
     L->tmp_bytes = std::max<size_t>(std::max(sort_bytes, scan_bytes), 16);
-    const bool ok = scratch_alloc(&L->keys[0], n) && scratch_alloc(&L->keys[1], n) && scratch_alloc(&L->vals[0], n) &&
-                    scratch_alloc(&L->vals[1], n) && scratch_alloc(&L->lpar, n) && scratch_alloc(&L->lbox, 8 * (size_t)n) &&
-                    scratch_alloc(&L->nbox, 8 * (size_t)n) && scratch_alloc(&L->cnt, n) && scratch_alloc(&L->front, n) &&
-                    scratch_alloc(&L->below, n) && scratch_alloc(&L->flag, n) && scratch_alloc(&L->widx, n) &&
-                    scratch_alloc(&L->wkids, n) && hipMalloc(&L->tmp, L->tmp_bytes) == hipSuccess;
+    const bool ok = scratch_alloc(L, &L->keys[0], n) && scratch_alloc(L, &L->keys[1], n) &&
+                    scratch_alloc(L, &L->vals[0], n) && scratch_alloc(L, &L->vals[1], n) && scratch_alloc(L, &L->lpar, n) &&
+                    scratch_alloc(L, &L->lbox, 8 * (size_t)n) && scratch_alloc(L, &L->nbox, 8 * (size_t)n) &&
+                    scratch_alloc(L, &L->cnt, n) && scratch_alloc(L, &L->front, n) && scratch_alloc(L, &L->below, n) &&
+                    scratch_alloc(L, &L->flag, n) && scratch_alloc(L, &L->widx, n) && scratch_alloc(L, &L->wkids, n) &&
+                    L->pool.alloc(&L->tmp, L->tmp_bytes) == hipSuccess;
     if (!ok) {
         scratch_release(L);
         c->err = "scene_rebuild_mesh: scratch allocation failed";
@@ -556,25 +544,26 @@ int lbvh_build(ctl_ctx* c, const float* d_pos, uint32_t n, void* nodes_, void* w
     float* nodes = static_cast<float*>(nodes_);
     float4* woop = static_cast<float4*>(woop_);
     WideNode* wide = static_cast<WideNode*>(wide_);
+    uint32_t* const res = L->d_res.get();
     const dim3 blk(kLB), g_tri((n + kLB - 1) / kLB);
     auto fail = [&](const char* m) { c->err = std::string("scene_rebuild_mesh: ") + m; return (int)CTL_ERR_HIP; };
     if (n == 1) {
-        hipLaunchKernelGGL(lbvh_single_kernel, dim3(1), dim3(1), 0, s, d_pos, nodes, woop, idx, wide, L->d_res);
+        hipLaunchKernelGGL(lbvh_single_kernel, dim3(1), dim3(1), 0, s, d_pos, nodes, woop, idx, wide, res);
     } else {
         const uint32_t ni = n - 1;
         const dim3 g_in((ni + kLB - 1) / kLB);
         if (hipMemsetAsync(L->cnt, 0, ni * sizeof(uint32_t), s) != hipSuccess ||
             hipMemsetAsync(L->flag, 0, ni * sizeof(uint32_t), s) != hipSuccess)
             return fail("memset failed");
-        hipLaunchKernelGGL(lbvh_init_kernel, dim3(1), dim3(1), 0, s, L->d_res, L->front, L->below);
-        hipLaunchKernelGGL(lbvh_box_kernel, dim3(std::min(g_tri.x, kBoxBlocks)), blk, 0, s, d_pos, n, L->d_res);
-        hipLaunchKernelGGL(lbvh_key_kernel, g_tri, blk, 0, s, d_pos, n, L->d_res, L->keys[0], L->vals[0]);
+        hipLaunchKernelGGL(lbvh_init_kernel, dim3(1), dim3(1), 0, s, res, L->front, L->below);
+        hipLaunchKernelGGL(lbvh_box_kernel, dim3(std::min(g_tri.x, kBoxBlocks)), blk, 0, s, d_pos, n, res);
+        hipLaunchKernelGGL(lbvh_key_kernel, g_tri, blk, 0, s, d_pos, n, res, L->keys[0], L->vals[0]);
         size_t tb = L->tmp_bytes;
         if (rocprim::radix_sort_pairs(L->tmp, tb, L->keys[0], L->keys[1], L->vals[0], L->vals[1], n, 0u, 64u, s) != hipSuccess)
             return fail("sort failed");
         hipLaunchKernelGGL(lbvh_tree_kernel, g_in, blk, 0, s, L->keys[1], n, nodes, L->lpar);
         hipLaunchKernelGGL(lbvh_leaf_kernel, g_tri, blk, 0, s, d_pos, L->vals[1], n, woop, idx, L->lbox);
-        hipLaunchKernelGGL(lbvh_fit_kernel, g_tri, blk, 0, s, n, nodes, L->lpar, L->lbox, L->nbox, L->cnt, L->d_res);
+        hipLaunchKernelGGL(lbvh_fit_kernel, g_tri, blk, 0, s, n, nodes, L->lpar, L->lbox, L->nbox, L->cnt, res);
         if (wide) {
             // level lv holds at most 4^lv nodes; the lists alternate between front and widx
             // (the scan fills widx after the last level)
@@ -584,7 +573,7 @@ int lbvh_build(ctl_ctx* c, const float* d_pos, uint32_t n, void* nodes_, void* w
                 const uint64_t most = lv < 12 ? std::min<uint64_t>(1ull << (2 * lv), ni) : ni;
                 const uint32_t blocks = (uint32_t)std::min<uint64_t>((most + kLB - 1) / kLB, kLevelBlocks);
                 hipLaunchKernelGGL(lbvh_wide_level_kernel, dim3(blocks), blk, 0, s, lv, nodes, L->nbox, lists[lv & 1],
-                                   lists[(lv + 1) & 1], L->below, L->flag, L->wkids, L->d_res);
+                                   lists[(lv + 1) & 1], L->below, L->flag, L->wkids, res);
             }
             tb = L->tmp_bytes;
             if (rocprim::exclusive_scan(L->tmp, tb, L->flag, L->widx, 0u, ni, rocprim::plus<uint32_t>(), s) != hipSuccess)
@@ -594,12 +583,12 @@ int lbvh_build(ctl_ctx* c, const float* d_pos, uint32_t n, void* nodes_, void* w
         }
     }
     if (hipGetLastError() != hipSuccess) return fail("launch failed");
-    if (hipMemcpyAsync(L->h_res, L->d_res, kLbvhResWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s) != hipSuccess)
+    if (hipMemcpyAsync(L->h_res.get(), res, kLbvhResWords * sizeof(uint32_t), hipMemcpyDeviceToHost, s) != hipSuccess)
         return fail("readback failed");
     return CTL_OK;
 }
 
-const uint32_t* lbvh_result(const ctl_ctx* c) { return c->lbvh ? c->lbvh->h_res : nullptr; }
-const uint32_t* lbvh_result_dev(const ctl_ctx* c) { return c->lbvh ? c->lbvh->d_res : nullptr; }
+const uint32_t* lbvh_result(const ctl_ctx* c) { return c->lbvh ? c->lbvh->h_res.get() : nullptr; }
+const uint32_t* lbvh_result_dev(const ctl_ctx* c) { return c->lbvh ? c->lbvh->d_res.get() : nullptr; }
 
 }  // namespace ctl

@@ -39,14 +39,11 @@ struct LumResult {                           // written by lum_final_kernel
 };
 
 struct ImageState {
-    uint32_t* d_filtered = nullptr;          // filtered image when the caller passes none
-    size_t filtered_cap = 0;                 // words
-    float* d_lum = nullptr;                  // kLumMaxGroups partials, then a LumResult
-    float* d_ftab = nullptr;                 // canonical filter: the per-axis factors by integer distance
-    size_t ftab_cap = 0;
+    DevArray<uint32_t> d_filtered;           // filtered image when the caller passes none
+    DevArray<float> d_lum;                   // kLumMaxGroups partials, then a LumResult
+    DevArray<float> d_ftab;                  // canonical filter: the per-axis factors by integer distance
     // NonLocalMeansFilter's members (NonLocalMeansFilter.h:96-99)
-    float* d_weights = nullptr;              // m_weightBuffer: 169 floats per pixel
-    size_t weights_cap = 0;                  // pixels allocated
+    DevArray<float> d_weights;               // m_weightBuffer: 169 floats per pixel
     uint32_t ww = 0, wh = 0;                 // image the weights were computed for
     bool weights_valid = false;
     int64_t last_passes = -1;                // last_iter_weight_update
@@ -365,13 +362,7 @@ inline uint32_t lum_groups(uint64_t n) {
 }  // namespace
 
 void image_free(ctl_ctx* c) {
-    ImageState* st = c->img;
-    if (!st) return;
-    if (st->d_filtered) (void)hipFree(st->d_filtered);
-    if (st->d_lum) (void)hipFree(st->d_lum);
-    if (st->d_ftab) (void)hipFree(st->d_ftab);
-    if (st->d_weights) (void)hipFree(st->d_weights);
-    delete st;
+    delete c->img;
     c->img = nullptr;
 }
 
@@ -386,9 +377,7 @@ inline unsigned blocks_of(uint64_t n) { return (unsigned)((n + kBlock - 1) / kBl
 int image_state(ctl_ctx* c) {
     if (c->img) return CTL_OK;
     ImageState* st = new ImageState();
-    const size_t bytes = (size_t)kLumMaxGroups * kLumFields * sizeof(float) + sizeof(LumResult);
-    if (hipMalloc(&st->d_lum, bytes) != hipSuccess) {
-        (void)hipGetLastError();
+    if (st->d_lum.grow((size_t)kLumMaxGroups * kLumFields, sizeof(LumResult)) != hipSuccess) {
         delete st;
         c->err = "image pipeline: luminance scratch allocation failed";
         return CTL_ERR_NOMEM;
@@ -400,31 +389,22 @@ int image_state(ctl_ctx* c) {
 // a device array that only grows (an allocation synchronises, so it happens
 // only when an image is larger than any before)
 template <class T>
-int grow(ctl_ctx* c, T*& p, size_t& cap, size_t need, const char* what) {
-    if (cap >= need) return CTL_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    if (hipMalloc(&p, need * sizeof(T)) != hipSuccess) {
-        (void)hipGetLastError();
-        p = nullptr;
-        c->err = std::string("image pipeline: ") + what + " allocation failed";
-        return CTL_ERR_NOMEM;
-    }
-    cap = need;
-    return CTL_OK;
+int grow(ctl_ctx* c, DevArray<T>& a, size_t need, const char* what) {
+    if (a.fits(need) || a.grow(need) == hipSuccess) return CTL_OK;
+    c->err = std::string("image pipeline: ") + what + " allocation failed";
+    return CTL_ERR_NOMEM;
 }
 
 LumResult* lum_result(ImageState* st) {
-    return reinterpret_cast<LumResult*>(st->d_lum + (size_t)kLumMaxGroups * kLumFields);
+    return reinterpret_cast<LumResult*>(st->d_lum.get() + (size_t)kLumMaxGroups * kLumFields);
 }
 
 int launch_luminance(ctl_ctx* c, const uint32_t* rgbe, uint32_t w, uint32_t h, const ctl_tonemap* tm, hipStream_t s) {
     ImageState* st = c->img;
     const uint64_t n = (uint64_t)w * h;
     const uint32_t G = lum_groups(n);
-    hipLaunchKernelGGL(lum_reduce_kernel, dim3(G), dim3(kBlock), 0, s, rgbe, (uint32_t)n, G, st->d_lum);
-    hipLaunchKernelGGL(lum_final_kernel, dim3(1), dim3(kBlock), 0, s, (const float*)st->d_lum, G, w, h, tm != nullptr,
+    hipLaunchKernelGGL(lum_reduce_kernel, dim3(G), dim3(kBlock), 0, s, rgbe, (uint32_t)n, G, st->d_lum.get());
+    hipLaunchKernelGGL(lum_final_kernel, dim3(1), dim3(kBlock), 0, s, (const float*)st->d_lum.get(), G, w, h, tm != nullptr,
                        tm ? tm->key : 0.0f, tm ? tm->burn : 0.0f, lum_result(st));
     CTL_HIP(c, hipGetLastError());
     return CTL_OK;
@@ -442,11 +422,11 @@ int launch_canonical(ctl_ctx* c, const ctl_pixel* fb, uint32_t w, uint32_t h, fl
         return (uint32_t)(fl < (float)(res - 1) ? fl : (float)(res - 1)) + 1u;
     };
     const uint32_t nx = reach(f.x_width, w), ny = reach(f.y_width, h);
-    if (int e = grow(c, st->d_ftab, st->ftab_cap, (size_t)nx + ny, "filter table")) return e;
+    if (int e = grow(c, st->d_ftab, (size_t)nx + ny, "filter table")) return e;
     const uint32_t tiles_x = (w + kTile - 1) / kTile, tiles_y = (h + kTile - 1) / kTile;
-    hipLaunchKernelGGL(filter_table_kernel, dim3(blocks_of((uint64_t)nx + ny)), dim3(kBlock), 0, s, f, nx, ny, st->d_ftab);
+    hipLaunchKernelGGL(filter_table_kernel, dim3(blocks_of((uint64_t)nx + ny)), dim3(kBlock), 0, s, f, nx, ny, st->d_ftab.get());
     hipLaunchKernelGGL(canonical_kernel, dim3(tiles_x * tiles_y), dim3(kBlock), 0, s, fb, w, h, tiles_x, splat, f.x_width,
-                       f.y_width, (const float*)st->d_ftab, nx, ny, out);
+                       f.y_width, (const float*)st->d_ftab.get(), nx, ny, out);
     CTL_HIP(c, hipGetLastError());
     return CTL_OK;
 }
@@ -471,22 +451,22 @@ int launch_nlm(ctl_ctx* c, const ctl_pixel* fb, const ctl_pixel_variance* var, u
         const bool force_update = !st->weights_valid || st->ww != w || st->wh != h;
         if (force_update || st->last_passes + 1 != (int64_t)num_passes || (num_passes % f.update_periodicity) == 0) {
             st->weights_valid = false;
-            if (int e = grow(c, st->d_weights, st->weights_cap, (size_t)n * (kW * kW), "NLM weight buffer")) {
+            if (int e = grow(c, st->d_weights, (size_t)n * (kW * kW), "NLM weight buffer")) {
                 st->last_passes = -1;
                 return e;
             }
             if (direct)
                 hipLaunchKernelGGL((nlm_kernel<false, true>), grid, block, 0, s, fb, var, w, h, tiles_x, splat, f.k,
-                                   f.sigma2_scale, st->d_weights, out);
+                                   f.sigma2_scale, st->d_weights.get(), out);
             else
                 hipLaunchKernelGGL((nlm_kernel<true, true>), grid, block, 0, s, fb, var, w, h, tiles_x, splat, f.k,
-                                   f.sigma2_scale, st->d_weights, out);
+                                   f.sigma2_scale, st->d_weights.get(), out);
             st->ww = w; st->wh = h;
             st->weights_valid = true;
         } else {
             const uint32_t rows = (h + kApplyRows - 1) / kApplyRows;
             hipLaunchKernelGGL(nlm_apply_kernel, dim3(tiles_x * rows), dim3(kApplyThreads), 0, s, fb, w, h, tiles_x,
-                               splat, (const float*)st->d_weights, out);
+                               splat, (const float*)st->d_weights.get(), out);
         }
     }
     CTL_HIP(c, hipGetLastError());
@@ -533,8 +513,8 @@ CTL_API ctl_status ctl_image_pipeline(ctl_ctx* c, const ctl_pixel* fb, const ctl
     ImageState* st = c->img;
     uint32_t* filtered = d_filtered;
     if (!filtered) {
-        if (int e = grow(c, st->d_filtered, st->filtered_cap, (size_t)n, "filtered image")) return e;
-        filtered = st->d_filtered;
+        if (int e = grow(c, st->d_filtered, (size_t)n, "filtered image")) return e;
+        filtered = st->d_filtered.get();
     }
     if (!filter) {
         hipLaunchKernelGGL(to_filtered_kernel, dim3(blocks_of(n)), dim3(kBlock), 0, s, fb, (uint32_t)n, splat, filtered);

@@ -39,10 +39,7 @@ namespace {
 constexpr uint32_t kDirtyTrees = CTL_DIRTY_BVH | CTL_DIRTY_NODES;
 
 void free_arrays(ctl_ctx* c) {
-    for (SceneArray& a : c->sarr) {
-        if (a.p) (void)hipFree(a.p);
-        a = SceneArray{};
-    }
+    for (SceneArray& a : c->sarr) a = SceneArray{};
 }
 
 // Array slot `a` receives `bytes` from the host plus `pad` zero bytes.  The
@@ -52,27 +49,22 @@ void free_arrays(ctl_ctx* c) {
 ctl_status put(ctl_ctx* c, int a, const void* src, size_t bytes, size_t pad, hipStream_t s) {
     SceneArray& A = c->sarr[a];
     const size_t need = std::max<size_t>(bytes + pad, 16);
-    if (A.cap < need) {
-        if (A.p) {
-            SD_HIP(c, hipDeviceSynchronize());
-            (void)hipFree(A.p);
-            A = SceneArray{};
-        }
-        if (hipMalloc(&A.p, need) != hipSuccess) {
-            A.p = nullptr;
+    if (!A.mem.fits(need)) {
+        if (A.mem) SD_HIP(c, hipDeviceSynchronize());
+        A.bytes = 0;
+        if (A.mem.grow(need) != hipSuccess) {
             c->err = "scene: hipMalloc of " + std::to_string(need) + " bytes failed";
             return CTL_ERR_NOMEM;
         }
-        A.cap = need;
     }
-    if (pad) SD_HIP(c, hipMemsetAsync(static_cast<char*>(A.p) + bytes, 0, pad, s));
-    if (bytes) SD_HIP(c, hipMemcpyAsync(A.p, src, bytes, hipMemcpyHostToDevice, s));
+    if (pad) SD_HIP(c, hipMemsetAsync(A.mem.get() + bytes, 0, pad, s));
+    if (bytes) SD_HIP(c, hipMemcpyAsync(A.mem.get(), src, bytes, hipMemcpyHostToDevice, s));
     A.bytes = bytes;
     return CTL_OK;
 }
 
 template <class T>
-const T* dptr(ctl_ctx* c, int a) { return reinterpret_cast<const T*>(c->sarr[a].p); }
+const T* dptr(ctl_ctx* c, int a) { return reinterpret_cast<const T*>(c->sarr[a].mem.get()); }
 
 bool bsdf_ext_type(uint32_t t) {
     return t == CTL_BSDF_DIELECTRIC || t == CTL_BSDF_THINDIELECTRIC || t == CTL_BSDF_CONDUCTOR ||

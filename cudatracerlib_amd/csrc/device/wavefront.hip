@@ -270,19 +270,14 @@ __global__ __launch_bounds__(kBlock) void wf_resolve_kernel(PathParams P, WfStat
 }
 
 template <class T>
-bool wf_alloc(ctl_ctx* c, T** p, size_t n) {
-    if (hipMalloc((void**)p, n * sizeof(T) + 16) != hipSuccess) return false;
-    c->wf_allocs.push_back((void*)*p);
-    return true;
+bool wf_alloc(ctl_ctx* c, T** p, size_t n) { return c->wf_pool.alloc(p, n, 16) == hipSuccess; }
+
+void wavefront_free(ctl_ctx* c) {
+    c->wf_pool.clear();
+    c->wf = WfState{};
 }
 
 }  // namespace
-
-void wavefront_free(ctl_ctx* c) {
-    for (void* p : c->wf_allocs) (void)hipFree(p);
-    c->wf_allocs.clear();
-    c->wf = WfState{};
-}
 
 int wavefront_pass(ctl_ctx* c, const PathParams& P, const SampleSlots& SS, bool stats, hipStream_t s) {
     const uint64_t items = pass_items_of(P);   // owned pixels + apron items

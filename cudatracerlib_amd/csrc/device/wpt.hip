@@ -51,18 +51,17 @@ struct WptBuffers {
     // queue counts per bounce: slot b = {payload rays, shadow rays} traced by bounce
     // b, written by bounce b-1's scan; kernels read them on the device, the host
     // reads them back a few bounces late only to stop issuing bounces
-    uint32_t* counts = nullptr;
-    uint32_t count_slots = 0;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    DevArray<uint32_t> counts;     // two per slot
+    Event ev[4];
     // h_counts is double-buffered over passes: done[b] is recorded after the last
     // count copy of the pass that used buffer b, and the pass two later waits on it
     // before it writes that buffer, so a late copy of a pass issued on another
     // stream cannot overwrite the counts a later pass reads
-    uint32_t* h_cnt[2] = {nullptr, nullptr};
-    hipEvent_t done[2] = {nullptr, nullptr};
+    PinnedArray<uint32_t> h_cnt[2];
+    Event done[2];
     bool done_pending[2] = {false, false};
     int cur_buf = 0;
-    std::vector<void*> allocs;
+    DevPool pool;                  // owns the raw device pointers above
 };
 constexpr int kWptLag = 2;   // bounces the host check trails the device by
 
@@ -411,27 +410,14 @@ __global__ __launch_bounds__(kBlock) void wpt_scatter_kernel(const uint32_t* __r
 }
 
 template <class T>
-bool wpt_alloc(WptBuffers* B, T** p, size_t n) {
-    if (hipMalloc((void**)p, n * sizeof(T) + 64) != hipSuccess) return false;
-    B->allocs.push_back((void*)*p);
-    return true;
-}
+bool wpt_alloc(WptBuffers* B, T** p, size_t n) { return B->pool.alloc(p, n, 64) == hipSuccess; }
 
 #define WPT_HIP(call) CTL_HIP_AS(c, call, "wpt: " #call)
 
 }  // namespace
 
 void wpt_free(ctl_ctx* c) {
-    WptBuffers* B = c->wpt;
-    if (!B) return;
-    for (void* p : B->allocs) (void)hipFree(p);
-    for (int b = 0; b < 2; b++) {
-        if (B->h_cnt[b]) (void)hipHostFree(B->h_cnt[b]);
-        if (B->done[b]) (void)hipEventDestroy(B->done[b]);
-    }
-    for (hipEvent_t e : B->ev)
-        if (e) (void)hipEventDestroy(e);
-    delete B;
+    delete c->wpt;
     c->wpt = nullptr;
 }
 
@@ -456,8 +442,8 @@ int wpt_pass(ctl_ctx* c, const ctl_wpt_params* prm, ctl_pixel* fb, hipStream_t s
                   wpt_alloc(B, &B->rays[1], n) && wpt_alloc(B, &B->hits, n) && wpt_alloc(B, &B->sec_tmp, n) &&
                   wpt_alloc(B, &B->sec, n) && wpt_alloc(B, &B->sec_hits, n) && wpt_alloc(B, &B->flags, n) &&
                   wpt_alloc(B, &B->blocks, nb_max);
-        for (hipEvent_t& e : B->ev) ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
-        for (hipEvent_t& e : B->done) ok = ok && hipEventCreateWithFlags(&e, hipEventDisableTiming) == hipSuccess;
+        for (Event& e : B->ev) ok = ok && e.create(hipEventDisableTiming) == hipSuccess;
+        for (Event& e : B->done) ok = ok && e.create(hipEventDisableTiming) == hipSuccess;
         if (!ok) { wpt_free(c); c->err = "wpt: buffer allocation failed"; return CTL_ERR_NOMEM; }
         B->capacity = items;
     }
@@ -487,21 +473,14 @@ int wpt_pass(ctl_ctx* c, const ctl_wpt_params* prm, ctl_pixel* fb, hipStream_t s
 
     // count slots for every bounce of the pass (+1 for the last scan's output)
     const uint32_t slots = (uint32_t)prm->max_path_length + 1u;
-    if (B->count_slots < slots) {
+    const size_t n_counts = 2 * (size_t)slots;
+    if (!B->counts.fits(n_counts) || !B->h_cnt[0].fits(n_counts) || !B->h_cnt[1].fits(n_counts)) {
         WPT_HIP(hipDeviceSynchronize());   // no count copy of an earlier pass in flight
-        uint32_t* dc = nullptr;
-        if (!wpt_alloc(B, &dc, 2 * (size_t)slots)) { c->err = "wpt: count allocation failed"; return CTL_ERR_NOMEM; }
+        if (B->counts.grow(n_counts, 64) != hipSuccess) { c->err = "wpt: count allocation failed"; return CTL_ERR_NOMEM; }
         for (int b = 0; b < 2; b++) {
-            if (B->h_cnt[b]) (void)hipHostFree(B->h_cnt[b]);
-            B->h_cnt[b] = nullptr;
             B->done_pending[b] = false;
-            if (hipHostMalloc((void**)&B->h_cnt[b], 2 * (size_t)slots * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess) {
-                c->err = "wpt: count allocation failed";
-                return CTL_ERR_NOMEM;
-            }
+            if (B->h_cnt[b].grow(n_counts) != hipSuccess) { c->err = "wpt: count allocation failed"; return CTL_ERR_NOMEM; }
         }
-        B->counts = dc;
-        B->count_slots = slots;
     }
     // this pass's host count buffer: the pass that used it last (two passes ago)
     // may still have copies in flight on its stream
@@ -511,11 +490,11 @@ int wpt_pass(ctl_ctx* c, const ctl_wpt_params* prm, ctl_pixel* fb, hipStream_t s
         WPT_HIP(hipEventSynchronize(B->done[hb]));
         B->done_pending[hb] = false;
     }
-    uint32_t* const h_counts = B->h_cnt[hb];
+    uint32_t* const h_counts = B->h_cnt[hb].get();
     const uint32_t n0 = (uint32_t)items;
     int cur = 0;
     hipLaunchKernelGGL(wpt_create_kernel, dim3(nb_max), dim3(kBlock), 0, s, c->scene, A, s1, s2, n0, B->rays[0],
-                       B->pay[0], B->counts);
+                       B->pay[0], B->counts.get());
     WPT_HIP(hipGetLastError());
     // The queue sizes stay on the device: every kernel of bounce b reads slot b,
     // the grids are sized for the largest queue (the pass's pixels) and idle
@@ -528,7 +507,7 @@ int wpt_pass(ctl_ctx* c, const ctl_wpt_params* prm, ctl_pixel* fb, hipStream_t s
     h_counts[0] = n0;   // slot 0 is written by wpt_create_kernel; its host copy is known
     h_counts[1] = 0u;
     for (int depth = 0;; depth++) {
-        const uint32_t* cnt = B->counts + 2 * depth;
+        const uint32_t* cnt = B->counts.get() + 2 * depth;
         if (depth >= kWptLag) ub = std::min(ub, h_counts[2 * (depth - kWptLag)]);
         const uint32_t nb = (ub + kBlock - 1) / kBlock;
         // FinishIteration: payload rays, then the secondary buffer (closest
@@ -547,11 +526,11 @@ int wpt_pass(ctl_ctx* c, const ctl_wpt_params* prm, ctl_pixel* fb, hipStream_t s
             };
             if (nee) launch(std::true_type{}); else launch(std::false_type{});
         });
-        hipLaunchKernelGGL(wpt_scan_kernel, dim3(1), dim3(kScanThreads), 0, s, B->blocks, cnt, B->counts + 2 * (depth + 1));
+        hipLaunchKernelGGL(wpt_scan_kernel, dim3(1), dim3(kScanThreads), 0, s, B->blocks, cnt, B->counts.get() + 2 * (depth + 1));
         hipLaunchKernelGGL(wpt_scatter_kernel, dim3(nb), dim3(kBlock), 0, s, cnt, B->flags, B->blocks, B->pay[cur],
                            B->rays[cur], B->sec_tmp, B->pay[1 - cur], B->rays[1 - cur], B->sec);
         WPT_HIP(hipGetLastError());
-        WPT_HIP(hipMemcpyAsync(h_counts + 2 * (depth + 1), B->counts + 2 * (depth + 1), 2 * sizeof(uint32_t),
+        WPT_HIP(hipMemcpyAsync(h_counts + 2 * (depth + 1), B->counts.get() + 2 * (depth + 1), 2 * sizeof(uint32_t),
                                hipMemcpyDeviceToHost, s));
         WPT_HIP(hipEventRecord(B->ev[depth % 4], s));
         cur = 1 - cur;
