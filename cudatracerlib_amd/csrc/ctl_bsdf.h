@@ -1071,7 +1071,8 @@ CTL_HD spec bsdf_f(const ctl_material& m, bsdf_rec& b, const dgeom& dg, const Te
         if (m.bsdf_type == CTL_BSDF_PLASTIC) Rd = R ? *R : diffuse_reflectance(m, dg, tex);
         res = mat_f(gm, ge, b, measure, Rd);
     } else {
-        res = rough_f(gm, b);
+        // roughdielectric::f is black under any measure but ESolidAngle (BSDF_Simple.cu:439-440)
+        res = measure != kESolidAngle ? mk3s(0.0f) : rough_f(gm, b);
     }
     if (flip) { b.wi.z *= -1.0f; b.wo.z *= -1.0f; }
     return res;
@@ -1083,7 +1084,9 @@ CTL_HD float bsdf_pdf(const ctl_material& m, bsdf_rec& b, const ctl_material* gm
     if (m.bsdf_type == CTL_BSDF_DIFFUSE) return diffuse_pdf(m, b);
     const bool flip = b.wi.z < 0 && m.two_sided;
     if (flip) b.wi.z *= -1.0f;
-    float res = EXT && m.bsdf_type != CTL_BSDF_ROUGHDIELECTRIC ? mat_pdf(gm, ge, b, measure) : rough_pdf(gm, b);
+    float res;
+    if (EXT && m.bsdf_type != CTL_BSDF_ROUGHDIELECTRIC) res = mat_pdf(gm, ge, b, measure);
+    else res = measure != kESolidAngle ? 0.0f : rough_pdf(gm, b);   // roughdielectric::pdf, BSDF_Simple.cu:375-376
     if (flip) { b.wi.z *= -1.0f; b.wo.z *= -1.0f; }
     return res;
 }

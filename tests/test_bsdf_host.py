@@ -74,7 +74,8 @@ def test_delta_queries_reach_every_branch():
 
 # ---------------------------------------------------------------------------------------------
 # roughconductor: its microfacet steps (mf_eval, mf_G, mf_smithG1, mf_sample) are the rough
-# dielectric's, pinned against the reference elsewhere; what is new is how they are combined.
+# dielectric's, held to a float64 reference from the papers in tests/test_microfacet_host.py (as is
+# the rough conductor itself); what is new is how they are combined.
 
 def _rough_dirs():
     """(wi, wo) with wi.z in [0.6, 0.95] and wo the mirror image of wi about a half vector tilted by
