@@ -118,7 +118,7 @@ struct Park {
     }
     // Partial loads and stores (the FULL kernels): after a trace the lane loads only
     // depth / specular and the sampler state; shade_hit reads the rest where it
-    // is used (common.h shade_hit, `pk`), and only what changed goes back.
+    // is used (shading.h shade_hit, `pk`), and only what changed goes back.
     __device__ __forceinline__ void load_core(PathVars& v, SamplerDev& rng) const {
         const uint32_t ds = geti(15);
         v.depth = (int)(ds >> 1); v.specular = (ds & 1u) != 0;
@@ -164,8 +164,7 @@ struct PathCtx {
     // one iteration of `while (depth++ < MaxPathLength)`; false = path done
     __device__ __forceinline__ bool bounce() {
         if (!(v.depth++ < P.max_path_length)) return false;
-        HitRec r2;   // traceRay (TraceHelper.cu:174-180)
-        r2.t = FLT_MAX; r2.tri = 0xffffffffu; r2.node = 0xffffffffu; r2.u = r2.v = 0.0f;
+        HitRec r2 = no_hit(FLT_MAX);   // traceRay (TraceHelper.cu:174-180)
         rays++;
         ok &= trace_one<0, STATS, SINGLE, WIDE, CTL_ALPHA_OF(FULL)>(S, v.rori, v.rdir, 0.0f, S.ray_eps, r2, st, &ts);
         if (r2.tri == 0xffffffffu) {
@@ -176,8 +175,7 @@ struct PathCtx {
         const bool cont = shade_hit<FULL, SINGLE>(S, P, rng, v, r2, sh);
         if (sh.valid) {
             const bool any = P.shadow_any_hit != 0;
-            HitRec h;
-            h.t = any ? sh.dist - S.ray_eps : FLT_MAX; h.tri = 0xffffffffu; h.node = 0xffffffffu; h.u = h.v = 0.0f;
+            HitRec h = no_hit(any ? sh.dist - S.ray_eps : FLT_MAX);
             rays++;
             if (any) ok &= trace_one<1, STATS, SINGLE, WIDE, CTL_ALPHA_OF(FULL)>(S, v.rori, sh.d, 0.0f, S.ray_eps, h, st, &ts,
                                                                                 sh.dist);
@@ -317,7 +315,8 @@ __global__ __launch_bounds__(kBlock) void path_kernel(DevScene S_arg, PathParams
     uint32_t px, py;
     if (work_pixel(P, g, px, py)) {
         const uint32_t idx = py * P.width + px;   // TracerBase::getPixelIndex (Tracer.h:89-97)
-        SamplerDev rng{s1, s2, P.nseq, P.len, idx % P.nseq, (idx / P.nseq) % P.nseq, 0, 0};
+        SamplerDev rng;
+        rng.init(s1, s2, P.nseq, P.len, idx);
         PathCtx<STATS, SINGLE, WIDE, FULL> C{S, P, rng, st, 0, TraceStats{0, 0, 0}, true, PathVars{}};
         f3 o, dw;
         const f2 pX = primary_ray(S, rng, px, py, o, dw);
@@ -335,6 +334,7 @@ __global__ __launch_bounds__(kBlock) void path_kernel(DevScene S_arg, PathParams
         PS.s[g] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);   // work item outside the image: no sample
     }
     wave_add_u64(&counters[0], rays);
+    // flush_counters written out: as a call, the STATS instantiations' registers change
     if (!ok) atomicAdd(&counters[1], 1ull);
     if (STATS) {
         wave_add_u64(&counters[2], ts.nodes);
@@ -423,7 +423,6 @@ __global__ __launch_bounds__(kBlock) void intersect_kernel(DevScene S_arg, int64
     T.done = true;
     bool haveRay = false, exhausted = false, ovf = false, seg2 = false;
     int64_t ray = 0;   // slot in its segment
-    const int lane = threadIdx.x & 63;
     while (true) {
         if (haveRay && T.done) {
             uint4 res = make_uint4((uint32_t)__float_as_int(T.h.t), 0xffffffffu, 0xffffffffu, 0u);
@@ -440,12 +439,9 @@ __global__ __launch_bounds__(kBlock) void intersect_kernel(DevScene S_arg, int64
         const bool need = !haveRay && !exhausted;
         const uint64_t mask = __ballot(need);
         if (mask && (__popcll(mask) >= CTL_REFILL_MIN || !__any(haveRay))) {
-            const int leader = __ffsll((unsigned long long)mask) - 1;
-            unsigned long long base = 0;
-            if (lane == leader) base = atomicAdd(cursor, (unsigned long long)__popcll(mask));
-            base = __shfl(base, leader);
+            const unsigned long long slot = wave_claim(cursor, mask);
             if (need) {
-                int64_t k = (int64_t)base + (int64_t)lanes_below(mask);
+                int64_t k = (int64_t)slot;
                 if (k < total) {
                     // band_w: the first segment is a row-major image of that width (the
                     // WavefrontPathTracer's camera rays); trace it in 8-row bands, column by
@@ -472,12 +468,7 @@ __global__ __launch_bounds__(kBlock) void intersect_kernel(DevScene S_arg, int64
         if (!__any(haveRay)) break;
         if (haveRay && !T.done) T.round(S, st, &ts);
     }
-    if (ovf) atomicAdd(&counters[1], 1ull);
-    if (STATS) {
-        wave_add_u64(&counters[2], ts.nodes);
-        wave_add_u64(&counters[3], ts.tris);
-        wave_add_u64(&counters[4], ts.inst);
-    }
+    flush_counters<STATS>(counters, ovf, ts);
 }
 
 // Primary rays of one pass in work order (the path kernels' first ray: pixel
@@ -494,7 +485,8 @@ __global__ __launch_bounds__(kBlock) void camera_ray_kernel(DevScene S_arg, Path
     float4 o4 = make_float4(0.0f, 0.0f, 0.0f, S.ray_eps), d4 = make_float4(0.0f, 0.0f, 1.0f, 0.0f);
     if (work_pixel(P, g, px, py)) {
         const uint32_t idx = py * P.width + px;
-        SamplerDev rng{s1, s2, P.nseq, P.len, idx % P.nseq, (idx / P.nseq) % P.nseq, 0, 0};
+        SamplerDev rng;
+        rng.init(s1, s2, P.nseq, P.len, idx);
         f3 o, d;
         (void)primary_ray(S, rng, px, py, o, d);
         o4 = make_float4(o.x, o.y, o.z, S.ray_eps);
@@ -522,9 +514,7 @@ __global__ __launch_bounds__(kBlock) void occluded_kernel(DevScene S_arg, int64_
     const float4* r4 = reinterpret_cast<const float4*>(rays + g);
     const float4 o = r4[0], d = r4[1];
     const float dist = d.w;
-    HitRec h;
-    h.t = ANYQ ? dist - S.ray_eps : FLT_MAX;
-    h.u = h.v = 0.0f; h.tri = 0xffffffffu; h.node = 0xffffffffu;
+    HitRec h = no_hit(ANYQ ? dist - S.ray_eps : FLT_MAX);
     bool ok = true;
     if (S.n_nodes != 0)
         ok = trace_one<ANYQ ? 1 : 0, false, SINGLE, WIDE, true>(S, mk3(o.x, o.y, o.z), mk3(d.x, d.y, d.z), 0.0f,

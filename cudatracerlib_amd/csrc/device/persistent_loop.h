@@ -37,17 +37,12 @@
     const long long prof_start = wall_clock64();
 #endif
     const bool shadowAny = P.shadow_any_hit != 0;
-    const int lane = threadIdx.x & 63;
     while (true) {
         const bool need = !active && !exhausted;
         const uint64_t mask = __ballot(need);
         if (mask) {
-            const int leader = __ffsll((unsigned long long)mask) - 1;
-            unsigned long long base = 0;
-            if (lane == leader) base = atomicAdd(cursor, (unsigned long long)__popcll(mask));
-            base = __shfl(base, leader);
+            const uint64_t k64 = wave_claim(cursor, mask);
             if (need) {
-                const uint64_t k64 = base + (uint64_t)lanes_below(mask);
                 if (k64 >= items) {
                     exhausted = true;
                 } else {
@@ -89,9 +84,7 @@
             continue;
         }
         if (active) {
-            HitRec h;
-            h.t = (shadowPhase && shadowAny) ? sh.dist - S.ray_eps : FLT_MAX;
-            h.u = h.v = 0.0f; h.tri = 0xffffffffu; h.node = 0xffffffffu;
+            HitRec h = no_hit((shadowPhase && shadowAny) ? sh.dist - S.ray_eps : FLT_MAX);
             rays++;
 #ifdef CTL_PROFILE_TRACE
             const long long pc0 = wall_clock64();
@@ -154,15 +147,10 @@
         }
     }
     wave_add_u64(&counters[0], rays);
-    if (!ok) atomicAdd(&counters[1], 1ull);
-    if (STATS) {
-        wave_add_u64(&counters[2], ts.nodes);
-        wave_add_u64(&counters[3], ts.tris);
-        wave_add_u64(&counters[4], ts.inst);
-    }
+    flush_counters<STATS>(counters, !ok, ts);
 #ifdef CTL_PROFILE_TRACE
     // wall-clock ticks (100 MHz) per wave: in the trace call site / in the kernel
-    if (lane == 0) {
+    if ((threadIdx.x & 63) == 0) {
         atomicAdd(&counters[5], (unsigned long long)prof_trace);
         atomicAdd(&counters[6], (unsigned long long)(wall_clock64() - prof_start));
     }

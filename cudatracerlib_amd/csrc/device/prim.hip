@@ -62,13 +62,13 @@ void prim_kernel(DevScene S_arg, PathParams P_arg, PrimParams Q, const float* s1
         uint32_t px, py;
         if (k >= items || !work_pixel(P, k, px, py)) continue;
         const uint32_t idx = py * P.width + px;   // g_SamplerData(rayidx), rayidx = y * w + x
-        SamplerDev rng{s1, s2, P.nseq, P.len, idx % P.nseq, (idx / P.nseq) % P.nseq, 0, 0};
+        SamplerDev rng;
+        rng.init(s1, s2, P.nseq, P.len, idx);
         const f2 pX = mk2((float)px, (float)py);
         (void)rng.next2();   // aperture sample of sampleRayDifferential (unused by PerspectiveSensor)
         f3 o, d;
         sensor_ray(S, pX, o, d);
-        HitRec h;
-        h.t = FLT_MAX; h.u = h.v = 0.0f; h.tri = 0xffffffffu; h.node = 0xffffffffu;
+        HitRec h = no_hit(FLT_MAX);
         rays++;
         if (S.n_nodes != 0) ok &= trace_one<0, false, SINGLE, WIDE, CTL_ALPHA_OF(FULL)>(S, o, d, 0.0f, S.ray_eps, h, st, &ts);
         spec L = mk3s(0.0f);
@@ -80,24 +80,11 @@ void prim_kernel(DevScene S_arg, PathParams P_arg, PrimParams Q, const float* s1
             } else {
                 // TraceResult::getBsdfSample (TraceResult.cu:16-45) + computePartials
                 const uint32_t node = SINGLE ? ~(uint32_t)S.start_node : h.node;
-                const ctl_triangle_data td = S.tri_data[h.tri];
-                const ctl_node* N = S.nodes + node;
                 dgeom dg;
-                dg.P = o + h.t * d;
-                fill_dg(td, load_m44(S.xf + 4 * node), mk2(h.u, h.v), P.half_quirk, LutDecode{S.normal_lut}, dg);
                 bsdf_rec b;
-                b.sampled_type = 0;
-                b.type_mask = kEAll;
-                b.wi = to_local(dg.sys, -d);
-                const uint32_t mat_index = ((td.w[1] >> 16) & 0xffu) + N->material_offset;
-                const ctl_material* gmat = S.mats + mat_index;
-                const ctl_material_ext* gext = CTL_EXT_OF(FULL) ? S.mats_ext + mat_index : nullptr;
-                const ctl_material mat = *gmat;
-                if (mat.two_sided && b.wi.z < 0) {
-                    dg.n = -dg.n;
-                    dg.sys.n = -dg.sys.n;
-                    b.wi.z *= -1.0f;
-                }
+                HitSurface sf;
+                const ctl_material mat =
+                    surface_at<FULL>(S, node, h.tri, mk2(h.u, h.v), o + h.t * d, d, P.half_quirk, dg, b, sf);
                 if (FULL) {
                     f3 co, dX, dY;
                     sensor_diff(S, pX, co, dX, dY);
@@ -122,12 +109,9 @@ void prim_kernel(DevScene S_arg, PathParams P_arg, PrimParams Q, const float* s1
                     // material (their bounce loop, PrimTracer.cu:68-97, is not built)
                     b.wo = mk3(0.0f, 0.0f, 1.0f);
                     const TexView tex{S.textures, S.tex_data};
-                    const spec f_avg = FULL ? bsdf_f<CTL_EXT_OF(FULL)>(mat, b, dg, &tex, nullptr, gmat, gext) : diffuse_f(mat, b);
-                    spec Le = mk3s(0.0f);   // TraceResult::Le -> DiffuseLight::eval (Light.cu:67-82)
-                    if (mat.node_light_index != 0xffffffffu) {
-                        const ctl_light Lt = S.lights[N->lights[mat.node_light_index]];
-                        Le = (dot(dg.sys.n, w) <= 0) ? mk3s(0.0f) : mk3(Lt.radiance[0], Lt.radiance[1], Lt.radiance[2]);
-                    }
+                    const spec f_avg = FULL ? bsdf_f<CTL_EXT_OF(FULL)>(mat, b, dg, &tex, nullptr, sf.gmat, sf.gext) : diffuse_f(mat, b);
+                    spec Le = mk3s(0.0f);   // TraceResult::Le
+                    if (mat.node_light_index != 0xffffffffu) Le = HitEmitter(S, sf.N, mat).Le(dg, w);
                     const spec through = mk3s(1.0f);   // Transmittance without media
                     if (Q.mode == CTL_PRIM_FIRST_LE || Q.mode == CTL_PRIM_FIRST_NON_DELTA_LE) {
                         L = through * Le;
@@ -138,12 +122,10 @@ void prim_kernel(DevScene S_arg, PathParams P_arg, PrimParams Q, const float* s1
                         if (S.n_lights) {
                             ShadowReq sh;
                             sh.valid = false;
-                            nee_sample<FULL>(S, rng, mat, b, dg, tex, sh, nullptr, gmat, gext);
+                            nee_sample<FULL>(S, rng, mat, b, dg, tex, sh, nullptr, sf.gmat, sf.gext);
                             if (sh.valid) {
                                 // KernelDynamicScene::Occluded (KernelDynamicScene.cu:70-80)
-                                HitRec hs;
-                                hs.t = sh.dist - S.ray_eps; hs.u = hs.v = 0.0f;
-                                hs.tri = 0xffffffffu; hs.node = 0xffffffffu;
+                                HitRec hs = no_hit(sh.dist - S.ray_eps);
                                 rays++;
                                 ok &= trace_one<1, false, SINGLE, WIDE, CTL_ALPHA_OF(FULL)>(S, dg.P, sh.d, 0.0f, S.ray_eps, hs, st, &ts,
                                                                                              sh.dist);
@@ -167,7 +149,7 @@ void prim_kernel(DevScene S_arg, PathParams P_arg, PrimParams Q, const float* s1
         if (Q.write_depth) depth[idx] = depth_d3d(h.t, Q.near_d, Q.far_d);   // g_DepthImage2.Store
     }
     wave_add_u64(&counters[0], rays);
-    if (!ok) atomicAdd(&counters[1], 1ull);
+    flush_counters<false>(counters, !ok, ts);   // no statistics instantiation
 }
 
 }  // namespace

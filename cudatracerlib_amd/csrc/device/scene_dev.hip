@@ -457,7 +457,7 @@ ctl_status commit_arrays(ctl_ctx* c, const ctl_scene_desc* d, uint32_t dirty, hi
         }
         if (S.alpha) S.full_shading = kShadeAlpha;
         if (S.env_index != 0xffffffffu) S.full_shading = kShadeEnv;
-        // the five further BSDF types run their own level (common.h), so every
+        // the five further BSDF types run their own level (shading.h), so every
         // other scene keeps the kernels it had
         c->has_delta = false;
         for (uint32_t i = 0; i < d->n_materials; i++) {

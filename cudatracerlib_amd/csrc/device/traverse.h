@@ -117,6 +117,11 @@ struct DevScene {
     const ctl_material_ext* mats_ext;   // parallel to mats (null when the desc has none)
 };
 
+// Index into mats of a triangle's material in node `node` (TraceResult.cu:16-20): its slot + the node's offset
+__device__ __forceinline__ uint32_t material_index(const DevScene& S, const ctl_triangle_data& td, uint32_t node) {
+    return ((td.w[1] >> 16) & 0xffu) + S.nodes[node].material_offset;
+}
+
 struct TraceStats {
     uint32_t nodes, tris, inst;
 #ifdef CTL_PROFILE_TRACE
@@ -143,6 +148,8 @@ struct HitRec {
     float t, u, v;
     uint32_t tri, node;
 };
+// nothing hit yet: search below t
+__device__ __forceinline__ HitRec no_hit(float t) { return HitRec{t, 0.0f, 0.0f, 0xffffffffu, 0xffffffffu}; }
 
 __device__ __forceinline__ int imin3(int a, int b, int c) { return min(min(a, b), c); }
 __device__ __forceinline__ int imax3(int a, int b, int c) { return max(max(a, b), c); }
@@ -292,7 +299,7 @@ struct Traverser4 {
     // at anyDist + slab_slack); ignored by closest-hit queries
     __device__ __forceinline__ void init(const DevScene& S, f3 o, f3 d, float smin, float tmn, float tmaxv,
                                          LaneStack& st, TraceStats* stats, float anyDist = -1.0f) {
-        h.t = tmaxv; h.u = h.v = 0.0f; h.tri = 0xffffffffu; h.node = 0xffffffffu;
+        h = no_hit(tmaxv);
         tcull = tmaxv;
         cullDist = anyDist;
         span_tmin = smin; tri_tmin = tmn;
@@ -325,7 +332,7 @@ struct Traverser4 {
     // TriangleData UV set 0 at (u, v) -> Material::AlphaTest (TraceHelper.cu:140-152)
     __device__ __forceinline__ bool alpha_survives(const DevScene& S, uint32_t gtri, float u, float v) const {
         const ctl_triangle_data td = S.tri_data[gtri];
-        const ctl_material& m = S.mats[((td.w[1] >> 16) & 0xffu) + S.nodes[instIdx].material_offset];
+        const ctl_material& m = S.mats[material_index(S, td, instIdx)];
         if (!m.alpha_state) return true;
         const bool q = (S.flags & CTL_SCENE_HALF_HOST_QUIRK) != 0;
         const f2 a = mk2(half_to_float(td.w[5] & 0xffffu, q), half_to_float(td.w[5] >> 16, q));

@@ -32,13 +32,8 @@ __device__ __forceinline__ uint32_t queue_push(uint32_t* count, bool want) {
     // wave-aggregated append: one atomic per wave
     const uint64_t mask = __ballot(want);
     if (!mask) return 0xffffffffu;
-    const int lane = threadIdx.x & 63;
-    const int leader = __ffsll((unsigned long long)mask) - 1;
-    uint32_t base = 0;
-    if (lane == leader) base = atomicAdd(count, (uint32_t)__popcll(mask));
-    base = __shfl(base, leader);
-    const uint32_t rank = lanes_below(mask);
-    return want ? base + rank : 0xffffffffu;
+    const uint32_t slot = wave_claim(count, mask);
+    return want ? slot : 0xffffffffu;
 }
 
 // Samples go to per-work-item slots (store_sample, common.h), folded into the
@@ -64,7 +59,7 @@ __global__ __launch_bounds__(kBlock) void wf_gen_kernel(DevScene S_arg, PathPara
         uint32_t idx = py * P.width + px;
         if (valid) {
             SamplerDev rng;
-            rng.init(s1, s2, P, idx, 0, 0);
+            rng.init(s1, s2, P.nseq, P.len, idx);
             pX = mk2((float)px, (float)py) + rng.next2();
             (void)rng.next2();   // aperture sample
             sensor_ray(S, pX, o, d);
@@ -111,7 +106,6 @@ __global__ __launch_bounds__(kBlock) void wf_trace_kernel(DevScene S_arg, WfStat
     T.done = true;
     bool haveRay = false, exhausted = false, ovf = false;
     uint32_t ray = 0;
-    const int lane = threadIdx.x & 63;
     while (true) {
         if (haveRay && T.done) {
             if (MODE == 0) {
@@ -128,12 +122,8 @@ __global__ __launch_bounds__(kBlock) void wf_trace_kernel(DevScene S_arg, WfStat
         const bool need = !haveRay && !exhausted;
         const uint64_t mask = __ballot(need);
         if (mask && (__popcll(mask) >= kWfRefillMin || !__any(haveRay))) {
-            const int leader = __ffsll((unsigned long long)mask) - 1;
-            uint32_t base = 0;
-            if (lane == leader) base = atomicAdd(cursor, (uint32_t)__popcll(mask));
-            base = __shfl(base, leader);
+            const uint32_t k = wave_claim(cursor, mask);
             if (need) {
-                const uint32_t k = base + lanes_below(mask);
                 if (k < count) {
                     ray = queue[k];
                     haveRay = true;
@@ -153,12 +143,7 @@ __global__ __launch_bounds__(kBlock) void wf_trace_kernel(DevScene S_arg, WfStat
         if (!__any(haveRay)) break;
         if (haveRay && !T.done) T.round(S, st, &ts);
     }
-    if (ovf) atomicAdd(&counters[1], 1ull);
-    if (STATS) {
-        wave_add_u64(&counters[2], ts.nodes);
-        wave_add_u64(&counters[3], ts.tris);
-        wave_add_u64(&counters[4], ts.inst);
-    }
+    flush_counters<STATS>(counters, ovf, ts);
 }
 
 template <int MODE>
@@ -216,7 +201,7 @@ __global__ __launch_bounds__(kBlock) void wf_shade_kernel(DevScene S_arg, PathPa
                 v.dudx = pt.x; v.dudy = pt.y; v.dvdx = pt.z; v.dvdy = pt.w;
             }
             SamplerDev rng;
-            rng.init(s1, s2, P, meta.x, meta.y & 0xffffu, meta.y >> 16);
+            rng.init(s1, s2, P.nseq, P.len, meta.x, meta.y & 0xffffu, meta.y >> 16);
             HitRec h;
             h.t = hit.x; h.u = hit.y; h.v = hit.z; h.tri = (uint32_t)__float_as_int(hit.w); h.node = W.hit_node[i];
             if (h.tri != 0xffffffffu) {

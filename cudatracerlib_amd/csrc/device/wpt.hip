@@ -79,9 +79,14 @@ struct WptArgs {
 __device__ __forceinline__ SamplerDev wpt_rng(const float* s1, const float2* s2, const WptArgs& A, uint32_t idx,
                                               uint32_t skip) {
     SamplerDev r;
-    r.s1 = s1; r.s2 = s2; r.nseq = A.nseq; r.len = A.len;
-    r.a = idx % A.nseq; r.b = (idx / A.nseq) % A.nseq;
-    r.d1 = skip % A.len; r.d2 = skip % A.len;   // draw counters mod len (SamplerDev)
+    r.init(s1, s2, A.nseq, A.len, idx, skip, skip);
+    return r;
+}
+
+__device__ __forceinline__ ctl_ray make_ray(f3 o, float tmin, f3 d, float tmax) {
+    ctl_ray r;
+    r.o[0] = o.x; r.o[1] = o.y; r.o[2] = o.z; r.tmin = tmin;
+    r.d[0] = d.x; r.d[1] = d.y; r.d[2] = d.z; r.tmax = tmax;
     return r;
 }
 
@@ -100,32 +105,13 @@ __global__ __launch_bounds__(kBlock) void wpt_create_kernel(DevScene S_arg, WptA
     (void)rng.next2();
     f3 o, d;
     sensor_ray(S, pX, o, d);
-    ctl_ray r;
-    r.o[0] = o.x; r.o[1] = o.y; r.o[2] = o.z; r.tmin = S.ray_eps;
-    r.d[0] = d.x; r.d[1] = d.y; r.d[2] = d.z; r.tmax = FLT_MAX;
-    rays[i] = r;
+    rays[i] = make_ray(o, S.ray_eps, d, FLT_MAX);
     WptPay p;
     p.a = make_float4(1.0f, 1.0f, 1.0f, 0.0f);   // throughput = W = Spectrum(1) (Sensor.cu:117)
     p.b = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     p.c = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float((uint32_t)half_round_int(x) | ((uint32_t)half_round_int(y) << 16)));
     p.d = make_uint4(0xffffffffu, 1u, 0u, i);
     pay[i] = p;
-}
-
-// KernelDynamicScene::sampleEmitter (KernelDynamicScene.cu:25-39)
-__device__ __forceinline__ uint32_t sample_emitter(const DevScene& S, f2& sample, float& emPdf) {
-    const uint32_t nl = S.n_lights < CTL_MAX_NUM_LIGHTS ? S.n_lights : CTL_MAX_NUM_LIGHTS;
-    uint32_t first = 0, cnt = nl;   // STL_upper_bound
-    while (cnt > 0) {
-        uint32_t c2 = cnt / 2, mid = first + c2;
-        if (!(sample.x < S.light_cdf[mid])) { first = mid + 1; cnt -= c2 + 1; }
-        else cnt = c2;
-    }
-    const uint32_t idx = first < nl ? first : nl - 1;
-    const float fU = S.light_cdf[idx], fL = idx > 0 ? S.light_cdf[idx - 1] : 0.0f;
-    sample.x = (sample.x - fL) / (fU - fL);
-    emPdf = fU - fL;
-    return idx;
 }
 
 // pathIterateKernel<NEXT_EVENT_EST> body for payload element j (WavefrontPathTracer.cu:56-148).
@@ -164,41 +150,29 @@ __global__ __launch_bounds__(kBlock) void wpt_iterate_kernel(DevScene S_arg, Wpt
             // TraceResult::getBsdfSample (TraceResult.cu:16-45); wo has no value yet -> (0,0,1)
             bsdf_rec b;
             b.wo = mk3(0.0f, 0.0f, 1.0f);
-            b.sampled_type = 0;
-            b.type_mask = kEAll;
             dgeom dg;
-            dg.P = ro + h.dist * rd;
+            HitSurface sf;
+            // surface_at's steps around hit_geometry written out: as one call, this kernel's registers change
+            b.sampled_type = 0; b.type_mask = kEAll;
             const uint32_t tri = (uint32_t)h.tri_idx, node = (uint32_t)h.node_idx;
             const ctl_triangle_data td = S.tri_data[tri];
-            const ctl_node* N = S.nodes + node;
-            fill_dg(td, load_m44(S.xf + 4 * node), bary, A.half_quirk, LutDecode{S.normal_lut}, dg);
+            sf.N = S.nodes + node;
+            hit_geometry(S, node, td, bary, ro + h.dist * rd, A.half_quirk, dg);
             dg.dudx = dg.dudy = dg.dvdx = dg.dvdy = 0.0f;
             dg.has_partials = false;   // no ray differentials in the wavefront tracer
             b.wi = to_local(dg.sys, -rd);
-            const uint32_t mat_index = ((td.w[1] >> 16) & 0xffu) + N->material_offset;
-            const ctl_material* gmat = S.mats + mat_index;
-            const ctl_material_ext* gext = CTL_EXT_OF(FULL) ? S.mats_ext + mat_index : nullptr;
-            const ctl_material mat = *gmat;
-            if (mat.two_sided && b.wi.z < 0) {
-                dg.n = -dg.n;
-                dg.sys.n = -dg.sys.n;
-                b.wi.z *= -1.0f;
-            }
+            const uint32_t mat_index = material_index(S, td, node);
+            sf.gmat = S.mats + mat_index;
+            sf.gext = CTL_EXT_OF(FULL) ? S.mats_ext + mat_index : nullptr;
+            const ctl_material mat = *sf.gmat;
+            if (mat.two_sided && b.wi.z < 0) { dg.n = -dg.n; dg.sys.n = -dg.sys.n; b.wi.z *= -1.0f; }
             const TexView tex{S.textures, S.tex_data};
             if (mat.node_light_index != 0xffffffffu) {
-                const uint32_t li = N->lights[mat.node_light_index];
-                const ctl_light Lt = S.lights[li];
+                const HitEmitter E(S, sf.N, mat);
                 float misWeight = 1.0f;
-                if (NEE && !(A.depth == 0 || specular)) {
-                    direct_rec dRec;   // DirectSamplingRecFromRay with the stored previous normal
-                    dRec.ref = ro; dRec.refN = LutDecode{S.normal_lut}(p.d.z); dRec.p = dg.P; dRec.n = dg.n;
-                    dRec.d = rd; dRec.dist = h.dist; dRec.measure = kESolidAngle;
-                    float direct_pdf = light_pdf_direct(Lt, dRec) * pdf_emitter(S, li);
-                    misWeight = power_heuristic(bpdf, direct_pdf);
-                }
-                f3 w = -rd;
-                spec Le = (dot(dg.sys.n, w) <= 0) ? mk3s(0.0f) : mk3(Lt.radiance[0], Lt.radiance[1], Lt.radiance[2]);
-                L = L + (misWeight * Le) * tp;
+                if (NEE && !(A.depth == 0 || specular))   // with the stored previous normal
+                    misWeight = emitter_mis(S, E, ro, LutDecode{S.normal_lut}(p.d.z), dg, rd, h.dist, bpdf);
+                L = L + (misWeight * E.Le(dg, -rd)) * tp;
             }
             bool surviveRR = true;
             if (A.depth >= A.rr_start_depth) {
@@ -206,14 +180,11 @@ __global__ __launch_bounds__(kBlock) void wpt_iterate_kernel(DevScene S_arg, Wpt
                 else surviveRR = false;
             }
             if (A.depth + 1 != A.max_path_length && surviveRR) {
-                // textured diffuse: one texture lookup for the BSDF sample and the NEE evaluation
-                // (plastic's m_diffuseReflectance takes the same path)
-                const bool texd = FULL && (mat.bsdf_type == CTL_BSDF_DIFFUSE || (CTL_EXT_OF(FULL) && mat.bsdf_type == CTL_BSDF_PLASTIC)) &&
-                                  mat.texture != 0xffffffffu;
+                const bool texd = textured_reflectance<FULL>(mat);
                 spec Rtex = mk3s(0.0f);
                 if (texd) Rtex = diffuse_reflectance(mat, dg, &tex);
                 const spec* Rp = texd ? &Rtex : nullptr;
-                spec f = FULL ? bsdf_sample<CTL_EXT_OF(FULL)>(mat, b, bpdf, rng.next2(), dg, &tex, Rp, gmat, gext)
+                spec f = FULL ? bsdf_sample<CTL_EXT_OF(FULL)>(mat, b, bpdf, rng.next2(), dg, &tex, Rp, sf.gmat, sf.gext)
                               : diffuse_sample(mat, b, bpdf, rng.next2());
                 specular = (b.sampled_type & kEDelta) != 0;
                 const f3 out = to_world(dg.sys, b.wo);
@@ -227,9 +198,7 @@ __global__ __launch_bounds__(kBlock) void wpt_iterate_kernel(DevScene S_arg, Wpt
                     float emPdf = 0.0f;
                     if (S.n_lights) {
                     const uint32_t lidx = sample_emitter(S, sample, emPdf);
-                    spec value = CTL_ENV_OF(FULL) && S.lights[lidx].kind == CTL_LIGHT_INFINITE
-                                     ? env_sample_direct(env_view(S), dRec, sample)
-                                     : light_sample_direct(S.lights[lidx], S.light_tris, S.light_tri_cdf, dRec, sample);
+                    spec value = sample_light_direct<FULL>(S, lidx, dRec, sample);
                     if (dRec.pdf != 0) {
                         dRec.pdf *= emPdf;
                         value = spec_div(value, emPdf);
@@ -239,28 +208,23 @@ __global__ __launch_bounds__(kBlock) void wpt_iterate_kernel(DevScene S_arg, Wpt
                     if (!spec_zero(value)) {
                         b.type_mask = kEAll & ~kEDelta;
                         b.wo = to_local(dg.sys, dRec.d);
-                        spec bsdfVal = FULL ? bsdf_f<CTL_EXT_OF(FULL)>(mat, b, dg, &tex, Rp, gmat, gext) : diffuse_f(mat, b);
-                        const float bsdfPdf = FULL ? bsdf_pdf<CTL_EXT_OF(FULL)>(mat, b, gmat, gext) : diffuse_pdf(mat, b);
+                        spec bsdfVal = FULL ? bsdf_f<CTL_EXT_OF(FULL)>(mat, b, dg, &tex, Rp, sf.gmat, sf.gext) : diffuse_f(mat, b);
+                        const float bsdfPdf = FULL ? bsdf_pdf<CTL_EXT_OF(FULL)>(mat, b, sf.gmat, sf.gext) : diffuse_pdf(mat, b);
                         const float directPdf = dRec.pdf;   // measure is ESolidAngle after sampleDirect
                         const float weight = power_heuristic(directPdf, bsdfPdf);
                         const spec dF = tp * value * bsdfVal * weight;
                         p.c.x = dF.x; p.c.y = dF.y; p.c.z = dF.z;
                         p.b.w = dRec.dist;
-                        ctl_ray sr;
-                        sr.o[0] = dg.P.x; sr.o[1] = dg.P.y; sr.o[2] = dg.P.z; sr.tmin = S.ray_eps;
                         // any-hit form: accept t < dist (1 - eps), the bound the compare
                         // in the next iteration tests the closest hit against
-                        sr.d[0] = dRec.d.x; sr.d[1] = dRec.d.y; sr.d[2] = dRec.d.z;
-                        sr.tmax = A.shadow_any ? p.b.w * (1 - S.ray_eps) : FLT_MAX;
-                        sec_tmp[j] = sr;
+                        sec_tmp[j] = make_ray(dg.P, S.ray_eps, dRec.d, A.shadow_any ? p.b.w * (1 - S.ray_eps) : FLT_MAX);
                         shadow = true;   // dIdx = its slot, set by the scatter
                     }
                     }
                 }
                 p.d.z = normal_encode16(dg.sys.n);
                 tp = tp * f;
-                next.o[0] = dg.P.x; next.o[1] = dg.P.y; next.o[2] = dg.P.z; next.tmin = S.ray_eps;
-                next.d[0] = out.x; next.d[1] = out.y; next.d[2] = out.z; next.tmax = FLT_MAX;
+                next = make_ray(dg.P, S.ray_eps, out, FLT_MAX);
                 cont = true;
             } else {
                 terminated = true;
@@ -268,6 +232,7 @@ __global__ __launch_bounds__(kBlock) void wpt_iterate_kernel(DevScene S_arg, Wpt
         } else {
             terminated = true;
             // misWeight * throughput * EvalEnvironment(ray) (WavefrontPathTracer.cu:144-157)
+            // (its own statement, not shading.h's env_miss: as a call, the kShadeMat kernel's registers change)
             if (CTL_ENV_OF(FULL) && S.env_index != 0xffffffffu) {
                 const EnvView E = env_view(S);
                 float misWeight = 1.0f;
