@@ -482,6 +482,8 @@ class HostScene:
         return r
 
     def add_area_light(self, node, local_material, radiance):
+        """DiffuseLight on material `local_material` of `node`.  The nodes of a mesh share its materials:
+        compile() refuses a mesh that carries a light and has more than one node."""
         arr = (C.c_float * 3)(*radiance)
         r = self._L.ctl_host_scene_add_area_light(self._h, node, local_material, arr)
         if r < 0:

@@ -244,22 +244,12 @@ void set_constants(ctl_ctx* c, const ctl_scene_desc* d, uint32_t dirty) {
     c->half_quirk = (d->flags & CTL_SCENE_HALF_HOST_QUIRK) != 0;
 }
 
-ctl_status commit_arrays(ctl_ctx* c, const ctl_scene_desc* d, uint32_t dirty, hipStream_t s);
+constexpr uint32_t kTreeBits = CTL_SCENE_BINARY_BVH | CTL_SCENE_WIDE_QUANT;
 
-// Every commit that changes the device scene (an array, or a constant such as
-// the camera) moves the scene epoch: render-ahead passes (ctl_render_pass)
-// belong to the epoch they were rendered in.
-ctl_status commit(ctl_ctx* c, const ctl_scene_desc* d, uint32_t dirty, hipStream_t s) {
-    DevScene before = c->scene;
-    const ctl_status r = commit_arrays(c, d, dirty, s);
-    if (r != CTL_OK || dirty != 0 || std::memcmp(&before, &c->scene, sizeof(DevScene)) != 0) c->scene_epoch++;
-    return r;
-}
-
-ctl_status commit_arrays(ctl_ctx* c, const ctl_scene_desc* d, uint32_t dirty, hipStream_t s) {
+// The array groups a commit of `dirty` really uploads, given what the context holds.
+uint32_t expand_dirty(const ctl_ctx* c, const ctl_scene_desc* d, uint32_t dirty) {
     // a change of the device tree format rebuilds the trees
-    const uint32_t tree_bits = CTL_SCENE_BINARY_BVH | CTL_SCENE_WIDE_QUANT;
-    if ((d->flags & tree_bits) != c->tree_flags) dirty |= kDirtyTrees;
+    if ((d->flags & kTreeBits) != c->tree_flags) dirty |= kDirtyTrees;
     // quantized trees are encoded together
     if ((d->flags & CTL_SCENE_WIDE_QUANT) && (dirty & kDirtyTrees)) dirty |= kDirtyTrees;
     // animated meshes: their rebuild plans describe the trees on the device (shape,
@@ -277,6 +267,106 @@ ctl_status commit_arrays(ctl_ctx* c, const ctl_scene_desc* d, uint32_t dirty, hi
     if (c->device_edited && (dirty & (kDirtyTrees | CTL_DIRTY_TRI_INDICES | CTL_DIRTY_MESHES | (regions_used ? CTL_DIRTY_WOOP : 0u))))
         dirty |= kDirtyTrees | CTL_DIRTY_TRI_INDICES | CTL_DIRTY_MESHES | CTL_DIRTY_TRI_DATA | CTL_DIRTY_WOOP |
                  CTL_DIRTY_LIGHTS | CTL_DIRTY_ENV;
+    return dirty;
+}
+
+// The trees a commit builds and the traversal stack the scene needs with them,
+// worked out from the desc (and, for the tree groups that stay, from the
+// context) before the commit changes anything: a scene whose stack bound passes
+// kStackMax is refused while the uploaded scene is still whole.
+struct TreePlan {
+    std::vector<WideNode> wn, sw;
+    std::vector<uint32_t> h_wbase;
+    std::vector<int> mesh_bin_bound, mesh_wide_bound;
+    int stack_mesh_bin = 0, stack_mesh_wide = 0, stack_top_bin = -1, stack_top_wide = -1, bound = 0;
+};
+
+// `dirty` as expand_dirty returns it; `fresh`: nothing is uploaded (ctl_scene_upload).
+ctl_status plan_trees(ctl_ctx* c, const ctl_scene_desc* d, uint32_t dirty, bool fresh, TreePlan& P) {
+    // 4-wide trees (host/bvh_wide.h) for the device traversal, unless the caller
+    // asks for the reference's binary visit order
+    const bool wide = (d->flags & CTL_SCENE_BINARY_BVH) == 0 && d->n_bvh_nodes > 0;
+    // the 4-wide mesh trees read the binary nodes, the leaf entries' last-in-leaf
+    // flags (counted leaves) and the per-mesh offsets
+    const bool mesh_trees = (dirty & (CTL_DIRTY_BVH | CTL_DIRTY_TRI_INDICES | CTL_DIRTY_MESHES)) != 0;
+    const bool top_tree = (dirty & CTL_DIRTY_NODES) != 0;
+    if (!fresh) {
+        P.stack_mesh_bin = c->stack_mesh_bin;
+        P.stack_mesh_wide = c->stack_mesh_wide;
+        P.stack_top_bin = c->stack_top_bin;
+        P.stack_top_wide = c->stack_top_wide;
+    }
+    try {
+        if (mesh_trees) {
+            P.h_wbase.assign(d->n_meshes, 0);
+            P.mesh_bin_bound.assign(d->n_meshes, 0);
+            P.mesh_wide_bound.assign(d->n_meshes, 0);
+            int mesh_bin = 0, mesh_wide = 0;
+            for (uint32_t m = 0; m < d->n_meshes && d->n_bvh_nodes > 0; m++) {
+                const size_t first = d->meshes[m].bvh_node_offset / 4;
+                if (first >= d->n_bvh_nodes) throw std::runtime_error("mesh BVH offset out of range");
+                P.mesh_bin_bound[m] = binary_stack_bound(d->bvh_nodes + first, d->n_bvh_nodes - first, 0, kStackMax);
+                mesh_bin = std::max(mesh_bin, P.mesh_bin_bound[m]);
+                if (!wide) continue;
+                P.h_wbase[m] = (uint32_t)P.wn.size();
+                // the mesh's entries start at bvh_indices_offset (meshes may be stored in any
+                // order); leaf children carry counts, each leaf bounded by its last-in-leaf flag
+                const uint64_t e0 = d->meshes[m].bvh_indices_offset;
+                if (e0 > d->n_tri_indices) throw std::runtime_error("mesh entry offset out of range");
+                collapse_wide(d->bvh_nodes + first, d->n_bvh_nodes - first, 0, P.wn, nullptr, d->tri_indices + e0,
+                              (size_t)(d->n_tri_indices - e0));
+                P.mesh_wide_bound[m] = wide_stack_bound(P.wn.data() + P.h_wbase[m], P.wn.size() - P.h_wbase[m], 0, kStackMax);
+                mesh_wide = std::max(mesh_wide, P.mesh_wide_bound[m]);
+            }
+            P.stack_mesh_bin = mesh_bin;
+            P.stack_mesh_wide = mesh_wide;
+        }
+        if (top_tree) {
+            P.stack_top_bin = P.stack_top_wide = -1;
+            if (d->n_nodes > 0 && d->scene_start_node >= 0) {
+                P.stack_top_bin = binary_stack_bound(d->scene_bvh_nodes, d->n_scene_bvh_nodes, d->scene_start_node, kStackMax);
+                if (wide) {
+                    collapse_wide(d->scene_bvh_nodes, d->n_scene_bvh_nodes, d->scene_start_node, P.sw);
+                    P.stack_top_wide = wide_stack_bound(P.sw.data(), P.sw.size(), 0, kStackMax);
+                }
+            }
+        }
+    } catch (const std::exception& e) {
+        c->err = std::string("scene_upload: ") + e.what();
+        return CTL_ERR_INVALID;
+    }
+    // Worst-case traversal stack for every traversal the scene can take (the
+    // 4-wide trees, and the binary trees of stats launches and
+    // CTL_SCENE_BINARY_BVH): a scene that could overflow the kStackMax entries
+    // of a lane is refused, so no ray can end early on a full stack.  Two
+    // levels: top-level stack + the pending top-level entry + the mesh stack.
+    // A scene whose bound is exactly kStackMax is accepted and traced in full.
+    P.bound = std::max(P.stack_mesh_bin, P.stack_mesh_wide);
+    if (P.stack_top_bin >= 0)
+        P.bound = std::max(P.stack_top_bin + 1 + P.stack_mesh_bin,
+                           P.stack_top_wide >= 0 ? P.stack_top_wide + 1 + P.stack_mesh_wide : 0);
+    if (P.bound > kStackMax) {
+        c->err = "scene_upload: the BVH needs a deeper traversal stack than " + std::to_string(kStackMax) + " entries";
+        return CTL_ERR_INVALID;
+    }
+    return CTL_OK;
+}
+
+ctl_status commit_arrays(ctl_ctx* c, const ctl_scene_desc* d, uint32_t dirty, hipStream_t s, TreePlan& P);
+
+// Every commit that changes the device scene (an array, or a constant such as
+// the camera) moves the scene epoch: render-ahead passes (ctl_render_pass)
+// belong to the epoch they were rendered in.  P: plan_trees of this commit.
+ctl_status commit(ctl_ctx* c, const ctl_scene_desc* d, uint32_t dirty, hipStream_t s, TreePlan& P) {
+    DevScene before = c->scene;
+    const ctl_status r = commit_arrays(c, d, dirty, s, P);
+    if (r != CTL_OK || dirty != 0 || std::memcmp(&before, &c->scene, sizeof(DevScene)) != 0) c->scene_epoch++;
+    return r;
+}
+
+ctl_status commit_arrays(ctl_ctx* c, const ctl_scene_desc* d, uint32_t dirty, hipStream_t s, TreePlan& P) {
+    const uint32_t tree_bits = kTreeBits;
+    dirty = expand_dirty(c, d, dirty);
     ctl_status r;
     if ((r = validate(c, d, dirty)) != CTL_OK) return r;
     if ((r = check_clean(c, d, dirty)) != CTL_OK) return r;
@@ -318,70 +408,23 @@ ctl_status commit_arrays(ctl_ctx* c, const ctl_scene_desc* d, uint32_t dirty, hi
         SD_HIP(c, hipStreamSynchronize(s));   // the table is a local
     }
 #undef PUT
-    // 4-wide trees (host/bvh_wide.h) for the device traversal, unless the caller
-    // asks for the reference's binary visit order
+    // the trees and the stack bound of this commit (plan_trees, checked before anything changed)
     const bool wide = (d->flags & CTL_SCENE_BINARY_BVH) == 0 && d->n_bvh_nodes > 0;
     const bool animated = d->n_anim_meshes > 0;
-    std::vector<WideNode> wn, sw;
-    // the 4-wide mesh trees read the binary nodes, the leaf entries' last-in-leaf
-    // flags (counted leaves) and the per-mesh offsets
     const bool mesh_trees = (dirty & (CTL_DIRTY_BVH | CTL_DIRTY_TRI_INDICES | CTL_DIRTY_MESHES)) != 0;
     const bool top_tree = (dirty & CTL_DIRTY_NODES) != 0;
-    try {
-        if (mesh_trees) {
-            c->h_wbase.assign(d->n_meshes, 0);
-            c->mesh_bin_bound.assign(d->n_meshes, 0);
-            c->mesh_wide_bound.assign(d->n_meshes, 0);
-            int mesh_bin = 0, mesh_wide = 0;
-            for (uint32_t m = 0; m < d->n_meshes && d->n_bvh_nodes > 0; m++) {
-                const size_t first = d->meshes[m].bvh_node_offset / 4;
-                if (first >= d->n_bvh_nodes) throw std::runtime_error("mesh BVH offset out of range");
-                c->mesh_bin_bound[m] = binary_stack_bound(d->bvh_nodes + first, d->n_bvh_nodes - first, 0, kStackMax);
-                mesh_bin = std::max(mesh_bin, c->mesh_bin_bound[m]);
-                if (!wide) continue;
-                c->h_wbase[m] = (uint32_t)wn.size();
-                // the mesh's entries start at bvh_indices_offset (meshes may be stored in any
-                // order); leaf children carry counts, each leaf bounded by its last-in-leaf flag
-                const uint64_t e0 = d->meshes[m].bvh_indices_offset;
-                if (e0 > d->n_tri_indices) throw std::runtime_error("mesh entry offset out of range");
-                collapse_wide(d->bvh_nodes + first, d->n_bvh_nodes - first, 0, wn, nullptr, d->tri_indices + e0,
-                              (size_t)(d->n_tri_indices - e0));
-                c->mesh_wide_bound[m] = wide_stack_bound(wn.data() + c->h_wbase[m], wn.size() - c->h_wbase[m], 0, kStackMax);
-                mesh_wide = std::max(mesh_wide, c->mesh_wide_bound[m]);
-            }
-            c->stack_mesh_bin = mesh_bin;
-            c->stack_mesh_wide = mesh_wide;
-        }
-        if (top_tree) {
-            c->stack_top_bin = c->stack_top_wide = -1;
-            if (d->n_nodes > 0 && d->scene_start_node >= 0) {
-                c->stack_top_bin = binary_stack_bound(d->scene_bvh_nodes, d->n_scene_bvh_nodes, d->scene_start_node, kStackMax);
-                if (wide) {
-                    collapse_wide(d->scene_bvh_nodes, d->n_scene_bvh_nodes, d->scene_start_node, sw);
-                    c->stack_top_wide = wide_stack_bound(sw.data(), sw.size(), 0, kStackMax);
-                }
-            }
-        }
-    } catch (const std::exception& e) {
-        c->err = std::string("scene_upload: ") + e.what();
-        return CTL_ERR_INVALID;
+    std::vector<WideNode>& wn = P.wn;
+    std::vector<WideNode>& sw = P.sw;
+    if (mesh_trees) {
+        c->h_wbase = P.h_wbase;
+        c->mesh_bin_bound = P.mesh_bin_bound;
+        c->mesh_wide_bound = P.mesh_wide_bound;
     }
-    // Worst-case traversal stack for every traversal the scene can take (the
-    // 4-wide trees, and the binary trees of stats launches and
-    // CTL_SCENE_BINARY_BVH): a scene that could overflow the kStackMax entries
-    // of a lane is refused, so no ray can end early on a full stack.  Two
-    // levels: top-level stack + the pending top-level entry + the mesh stack.
-    {
-        int bound = std::max(c->stack_mesh_bin, c->stack_mesh_wide);
-        if (c->stack_top_bin >= 0)
-            bound = std::max(c->stack_top_bin + 1 + c->stack_mesh_bin,
-                             c->stack_top_wide >= 0 ? c->stack_top_wide + 1 + c->stack_mesh_wide : 0);
-        if (bound > kStackMax) {
-            c->err = "scene_upload: the BVH needs a deeper traversal stack than " + std::to_string(kStackMax) + " entries";
-            return CTL_ERR_INVALID;
-        }
-        c->stack_bound = bound;
-    }
+    c->stack_mesh_bin = P.stack_mesh_bin;
+    c->stack_mesh_wide = P.stack_mesh_wide;
+    c->stack_top_bin = P.stack_top_bin;
+    c->stack_top_wide = P.stack_top_wide;
+    c->stack_bound = P.bound;
     if (wide && (mesh_trees || top_tree)) {
         // 64-B quantized nodes on request (not when the refit will rewrite float nodes)
         const bool quant = (d->flags & CTL_SCENE_WIDE_QUANT) != 0 && !animated;
@@ -535,9 +578,13 @@ CTL_API ctl_status ctl_scene_upload(ctl_ctx* c, const ctl_scene_desc* d) {
     if (hipSetDevice(c->device) != hipSuccess) { c->err = "scene_upload: hipSetDevice failed"; return CTL_ERR_HIP; }
     ctl_status r = validate(c, d, CTL_DIRTY_ALL);
     if (r != CTL_OK) return r;
+    // a scene whose trees are malformed or need a deeper stack than the traversal has is refused
+    // here, with the scene uploaded before still in place
+    TreePlan P;
+    if ((r = plan_trees(c, d, CTL_DIRTY_ALL, true, P)) != CTL_OK) return r;
     if (hipDeviceSynchronize() != hipSuccess) { c->err = "scene_upload: device synchronisation failed"; return CTL_ERR_HIP; }
     free_scene(c);
-    r = commit(c, d, CTL_DIRTY_ALL, nullptr);
+    r = commit(c, d, CTL_DIRTY_ALL, nullptr, P);
     if (r == CTL_OK && hipStreamSynchronize(nullptr) != hipSuccess) { c->err = "scene_upload: copy failed"; r = CTL_ERR_HIP; }
     if (r != CTL_OK) { std::string e = c->err; free_scene(c); c->err = e; return r; }
     c->has_scene = true;
@@ -552,8 +599,10 @@ CTL_API ctl_status ctl_scene_update(ctl_ctx* c, const ctl_scene_desc* d, uint32_
     // refusals that leave the uploaded scene as it was
     ctl_status r = validate(c, d, dirty);
     if (r == CTL_OK) r = check_clean(c, d, dirty);
+    TreePlan P;
+    if (r == CTL_OK) r = plan_trees(c, d, expand_dirty(c, d, dirty), false, P);
     if (r != CTL_OK) return r;
-    r = commit(c, d, dirty, reinterpret_cast<hipStream_t>(stream));
+    r = commit(c, d, dirty, reinterpret_cast<hipStream_t>(stream), P);
     if (r != CTL_OK) {   // the device scene may be half updated: drop it
         std::string e = c->err;
         (void)hipDeviceSynchronize();

@@ -641,6 +641,22 @@ CTL_API ctl_status ctl_host_scene_compile(ctl_host_scene* s, uint32_t threads, c
         s->light_tri_cdf.insert(s->light_tri_cdf.end(), cdf.begin(), cdf.end());
         s->klights.push_back(kl);
     }
+    // The instances of a mesh share its materials, and an emitting material finds its light through
+    // the node that was hit (nodes[n].lights[node_light_index]): a node of the mesh without that slot
+    // would send the shading to light 0xffffffff.  The loop above fills the slot of the first lit
+    // node only (the material's index is taken by then), so a lit mesh may have one node: neither a
+    // light on one of its instances nor a light on each of them compiles.
+    for (const ctl_node& kn : s->knodes) {
+        const size_t nm = s->meshes[kn.mesh_index].materials.size();
+        for (size_t k = 0; k < nm; k++) {
+            const uint32_t li = s->materials[kn.material_offset + k].node_light_index;
+            if (li != 0xffffffffu && (li >= 2 || kn.lights[li] == 0xffffffffu)) {
+                set_host_error("compile: a mesh whose material carries an area light must have one node only "
+                               "(its instances share the material, and only the first lit node gets the light's slot)");
+                return CTL_ERR_INVALID;
+            }
+        }
+    }
     // DynamicScene::setEnvironementMap: the InfiniteLight goes after the area lights
     // (m_uEnvMapIndex); its constructor's tables and Update()'s scene sphere
     uint32_t envIndex = 0xffffffffu;

@@ -1065,8 +1065,14 @@ CTL_API ctl_status ctl_reset_rays(ctl_ctx* ctx, void* stream);
 CTL_API ctl_status ctl_sync(ctl_ctx* ctx, void* stream);
 
 /* Worst-case traversal stack (entries per lane) of the uploaded scene over
- * every traversal it can take; ctl_scene_upload refuses scenes above the
- * device stack depth (128).  0 without a scene. */
+ * every traversal it can take, sentinels included; one level: the mesh tree's
+ * bound, two levels: instance tree + the pending instance-level entry + mesh
+ * tree.  128 is the limit: a scene whose bound is exactly 128 is supported and
+ * traced in full (a ray may really build a stack of 128 entries on one level;
+ * on two levels the deepest reachable stack is one short of the bound), and
+ * ctl_scene_upload / ctl_scene_update refuse a scene whose bound is 129 or more
+ * before they change anything, so the scene uploaded before stays in place and
+ * keeps tracing as it did.  0 without a scene. */
 CTL_API int32_t ctl_scene_stack_bound(const ctl_ctx* ctx);
 
 /* Traversal statistics for the roofline's algorithmic byte count (same kernel
@@ -1133,7 +1139,10 @@ CTL_API int32_t ctl_host_scene_add_texture(ctl_host_scene* s, const uint32_t* rg
                                            const float scale[3]);
 CTL_API int32_t ctl_host_scene_add_node(ctl_host_scene* s, uint32_t mesh, const float* xf16);
 /* Marks material `local_material` of `node` as a DiffuseLight with constant
- * radiance (DynamicScene::CreateLight on a mesh part). Returns the light index. */
+ * radiance (DynamicScene::CreateLight on a mesh part). Returns the light index.
+ * The nodes of a mesh share its materials, so a mesh with a lit material may
+ * have one node only: ctl_host_scene_compile refuses a lit mesh with further
+ * instances (give each lit instance a mesh of its own). */
 CTL_API int32_t ctl_host_scene_add_area_light(ctl_host_scene* s, uint32_t node, uint32_t local_material,
                                               const float radiance[3]);
 /* PerspectiveSensor: position, target, up, fov (degrees), near/far, resolution. */

@@ -25,6 +25,12 @@ SHADING_ENTRIES = ("oracle_render_pass", "oracle_render_pass_events", "oracle_pr
                    "oracle_bsdf_eval")
 
 
+# the batch entries, with and without the per-ray traversal stack depth; they refuse (OracleError)
+# a query that needs more than the product's kStackMax stack entries (device/traverse.h)
+DEPTH_ENTRIES = ("oracle_trace", "oracle_intersect", "oracle_occluded", "oracle_trace_depth", "oracle_intersect_depth",
+                 "oracle_occluded_depth")
+
+
 class OracleError(RuntimeError):
     """An oracle entry refused its input (oracle_last_error)."""
 
@@ -52,11 +58,19 @@ def load():
         "oracle_sampler_draws": (None, [vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_uint32, vp]),
         "oracle_camera": (None, [vp, vp, vp, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_uint32,
                                  C.POINTER(Camera)]),
-        "oracle_trace": (None, [C.POINTER(SceneDesc), C.c_int64, vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp,
+        "oracle_trace": (C.c_int32, [C.POINTER(SceneDesc), C.c_int64, vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp,
                                 C.c_int32]),
-        "oracle_intersect": (None, [C.POINTER(SceneDesc), C.c_int64, vp, vp, C.c_int32, C.c_int32, C.c_int32]),
-        "oracle_occluded": (None, [C.POINTER(SceneDesc), C.c_int64, vp, vp, C.c_int32, C.c_int32, C.c_int32,
+        "oracle_intersect": (C.c_int32, [C.POINTER(SceneDesc), C.c_int64, vp, vp, C.c_int32, C.c_int32, C.c_int32]),
+        "oracle_occluded": (C.c_int32, [C.POINTER(SceneDesc), C.c_int64, vp, vp, C.c_int32, C.c_int32, C.c_int32,
                                    C.c_int32]),
+        "oracle_trace_depth": (C.c_int32, [C.POINTER(SceneDesc), C.c_int64, vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp,
+                                           vp, C.c_int32, vp]),
+        "oracle_intersect_depth": (C.c_int32, [C.POINTER(SceneDesc), C.c_int64, vp, vp, C.c_int32, C.c_int32,
+                                               C.c_int32, vp]),
+        "oracle_occluded_depth": (C.c_int32, [C.POINTER(SceneDesc), C.c_int64, vp, vp, C.c_int32, C.c_int32, C.c_int32,
+                                              C.c_int32, vp]),
+        "oracle_depth_peak": (C.c_int32, []),
+        "oracle_depth_peak_reset": (None, []),
         "oracle_brute_force": (None, [C.POINTER(SceneDesc), C.c_int64, vp, vp, vp, C.c_int32]),
         "oracle_render_pass": (C.c_uint64, [C.POINTER(SceneDesc), C.POINTER(PTParams), C.c_uint64, vp, C.c_int32,
                                             C.c_int32, C.c_uint32, vp]),
@@ -95,7 +109,7 @@ def load():
             raise OracleError(msg or func.__name__ + " failed")
         return result
 
-    for name in SHADING_ENTRIES:
+    for name in SHADING_ENTRIES + DEPTH_ENTRIES:
         getattr(L, name).errcheck = refused
     _lib = L
     return L

@@ -85,6 +85,41 @@ const int EntrypointSentinel = 0x76543210;
 
 struct Stats { uint64_t nodes = 0, tris = 0, inst = 0; };
 
+// The product's stack contract (device/traverse.h kStackMax): one stack of 128
+// entries over both levels, sentinels included.  The reference's own array is
+// 64 entries per level (BVHTraversal.h:124); the oracle follows the product, so
+// every scene the upload accepts can be checked.
+const int kStackMax = 128;
+
+// Stack depth probe.  The size of the product's single stack (sentinels
+// included) at each push of the traversal running on this thread: `base` is
+// what lies under the running level (the instance level's entries, the pending
+// node and nothing else; the mesh level's own sentinel counts in its sp),
+// `peak` the largest size since the caller cleared it, `run` the largest over
+// the thread's life (folded into g_depth_peak, oracle_depth_peak).  A push
+// past kStackMax is a refusal (stack_refusal), never a write past the array.
+struct DepthProbe { int base = 0, peak = 0, run = 0; bool refused = false; };
+thread_local DepthProbe tl_depth;
+std::atomic<int> g_depth_peak{0};
+std::atomic<bool> g_stack_refused{false};
+void stack_refusal();   // oracle_last_error's message, set below
+// true if the stack may hold `size` entries
+inline bool depth_note(int size) {
+    DepthProbe& p = tl_depth;
+    if (size > kStackMax) {
+        if (!p.refused) stack_refusal();
+        p.refused = true;
+        return false;
+    }
+    if (size > p.peak) p.peak = size;
+    if (size > p.run) {
+        p.run = size;
+        int g = g_depth_peak.load();
+        while (size > g && !g_depth_peak.compare_exchange_weak(g, size)) {}
+    }
+    return true;
+}
+
 // TracerayTemplate, pointer overload (BVHTraversal.h:122-232).  spanTmin is 0
 // for traceRay and the ray's tmin for the batch kernel (TraceHelper.cu:469).
 // Boxes are culled against rayT, the current hit (the reference), or against
@@ -96,10 +131,14 @@ bool traceray_template(V3 ori, V3 dir, float& rayT, float spanTmin, const CLB& c
     if (startNode < 0) return clb(~startNode);
     bool found = false;
     // index 1 holds the sentinel; index 0 only absorbs the pop of an already
-    // popped sentinel (the reference would read before its array there)
-    int traversalStack[64 + 3];
+    // popped sentinel (the reference would read before its array there).  Sized
+    // for the product's contract, not the reference's 64: sp never passes
+    // kStackMax (depth_note), the two slots above it are guards.
+    int traversalStack[kStackMax + 3];
     traversalStack[0] = EntrypointSentinel;
     traversalStack[1] = EntrypointSentinel;
+    const int depthBase = tl_depth.base;   // entries of the level above (0 at the top)
+    depth_note(depthBase + 1);
     const float ooeps = powf(2.0f, -80.0f);   // math::exp2 host branch (MathFunc.h:240-245)
     float idirx = 1.0f / (fabsf(dir.x) > ooeps ? dir.x : o_copysign(ooeps, dir.x));
     float idiry = 1.0f / (fabsf(dir.y) > ooeps ? dir.y : o_copysign(ooeps, dir.y));
@@ -142,8 +181,9 @@ bool traceray_template(V3 ori, V3 dir, float& rayT, float spanTmin, const CLB& c
                 nodeAddr = traverseChild0 ? c0i : c1i;
                 if (traverseChild0 && traverseChild1) {
                     if (swp) std::swap(nodeAddr, c1i);
+                    // a full stack ends this level's traversal (refusal: the entry reports it)
+                    if (!depth_note(depthBase + sp + 1)) return found;
                     traversalStack[++sp] = c1i;
-                    if (sp > 65) { std::fprintf(stderr, "oracle: traversal stack overflow\n"); std::abort(); }
                 }
             }
             if (nodeAddr < 0 && leafAddr >= 0) {
@@ -153,7 +193,12 @@ bool traceray_template(V3 ori, V3 dir, float& rayT, float spanTmin, const CLB& c
             if (!(leafAddr >= 0)) break;   // host branch: mask = leafAddr >= 0
         }
         while (leafAddr < 0) {
-            if (leafAddr != -214783648) found |= clb(~leafAddr);   // sic, BVHTraversal.h:221
+            if (leafAddr != -214783648) {   // sic, BVHTraversal.h:221
+                // under a mesh entered from here: this level's entries and the pending node
+                tl_depth.base = depthBase + sp + 1;
+                found |= clb(~leafAddr);
+                tl_depth.base = depthBase;
+            }
             leafAddr = nodeAddr;
             if (nodeAddr < 0) nodeAddr = traversalStack[sp--];
         }
@@ -372,8 +417,9 @@ bool trace_two_level_wide(const SceneView& S, V3 ori, V3 dir, float spanTmin, fl
     const float* tris = reinterpret_cast<const float*>(d->woop_tris);
     const bool single = d->scene_start_node < 0;
     std::vector<int> stack;
-    stack.reserve(64);
+    stack.reserve(kStackMax);
     stack.push_back(EntrypointSentinel);
+    depth_note(1);
     auto pop = [&]() -> int {
         if (stack.empty()) return EntrypointSentinel;
         const int v = stack.back();
@@ -477,6 +523,8 @@ bool trace_two_level_wide(const SceneView& S, V3 ori, V3 dir, float spanTmin, fl
             cx(0, 1); cx(2, 3); cx(0, 2); cx(1, 3); cx(1, 2);
             int m = 0;
             for (int i = 0; i < 4; i++) m += k[i] != 0x7fffffff;
+            // the product's one stack over both levels: a push past kStackMax is a refusal
+            if (m > 1 && !depth_note((int)stack.size() + m - 1)) return found;
             for (int i = m - 1; i >= 1; i--) stack.push_back(c[i]);
             int next = m > 0 ? c[0] : pop();
             if (next < 0 && leafAddr >= 0) {   // postpone one leaf
@@ -494,6 +542,7 @@ bool trace_two_level_wide(const SceneView& S, V3 ori, V3 dir, float spanTmin, fl
             } else {
                 if (leafAddr != -214783648) {
                     enter((uint32_t)~leafAddr);
+                    if (!depth_note((int)stack.size() + 2)) return found;
                     stack.push_back(nodeAddr);   // pending top-level work
                     meshSent = stack.size();
                     stack.push_back(EntrypointSentinel);
@@ -828,6 +877,12 @@ bool material_restated(const ctl_scene_desc* d, uint32_t i, std::string& why) {
 std::mutex g_err_mtx;
 std::string g_err;
 void set_error(const std::string& s) { std::lock_guard<std::mutex> g(g_err_mtx); g_err = s; }
+// a traversal needed more than the product's kStackMax stack entries (depth_note)
+void stack_refusal() {
+    g_stack_refused = true;
+    set_error("oracle: the BVH needs a deeper traversal stack than " + std::to_string(kStackMax) +
+              " entries (the product's upload refuses such a scene)");
+}
 // true (and the message kept for oracle_last_error) if the scene holds a material the oracle cannot shade
 bool shading_refusal(const ctl_scene_desc* d, const char* entry) {
     std::string why;
@@ -1931,10 +1986,15 @@ void oracle_camera(const float* pos, const float* tar, const float* up, float fo
 
 // traceRay semantics (mode 0) or batch semantics (mode 1 closest, 2 any-hit).
 // Outputs t,u,v,tri,node per ray; stats[0..3] = rays, inner nodes, tri tests, instance entries.
-void oracle_trace(const ctl_scene_desc* desc, int64_t n, const ctl_ray* rays, int32_t mode, int32_t tie,
-                  float* out_t, float* out_u, float* out_v, uint32_t* out_tri, uint32_t* out_node, uint64_t* stats,
-                  int32_t threads) {
+// depth (may be NULL): per ray, the largest size the product's traversal stack
+// reaches on it, sentinels included (DepthProbe).  Returns nonzero, with
+// oracle_last_error set, if a ray needed more than kStackMax entries; that
+// ray's outputs mean nothing.
+static int32_t trace_batch(const ctl_scene_desc* desc, int64_t n, const ctl_ray* rays, int32_t mode, int32_t tie,
+                           float* out_t, float* out_u, float* out_v, uint32_t* out_tri, uint32_t* out_node,
+                           uint64_t* stats, int32_t threads, int32_t* depth) {
     SceneView S{desc};
+    std::atomic<bool> refused{false};
     if (threads <= 0) threads = (int)std::thread::hardware_concurrency();
     std::atomic<int64_t> next{0};
     std::mutex mtx;
@@ -1950,6 +2010,8 @@ void oracle_trace(const ctl_scene_desc* desc, int64_t n, const ctl_ray* rays, in
                 const ctl_ray& r = rays[i];
                 V3 o = v3(r.o[0], r.o[1], r.o[2]), dd = v3(r.d[0], r.d[1], r.d[2]);
                 Hit h;
+                tl_depth.peak = 0;
+                tl_depth.refused = false;
                 if (mode == 0) {
                     trace_ray(S, o, dd, h, tie, &st);
                 } else {
@@ -1958,6 +2020,8 @@ void oracle_trace(const ctl_scene_desc* desc, int64_t n, const ctl_ray* rays, in
                 }
                 nr++;
                 out_t[i] = h.t; out_u[i] = h.u; out_v[i] = h.v; out_tri[i] = h.tri; out_node[i] = h.node;
+                if (depth) depth[i] = tl_depth.peak;
+                if (tl_depth.refused) refused = true;
             }
         }
         std::lock_guard<std::mutex> g(mtx);
@@ -1967,15 +2031,34 @@ void oracle_trace(const ctl_scene_desc* desc, int64_t n, const ctl_ray* rays, in
     for (int i = 0; i < threads; i++) ts.emplace_back(worker);
     for (auto& t : ts) t.join();
     if (stats) for (int i = 0; i < 4; i++) stats[i] = acc[i];
+    return refused ? 1 : 0;
 }
+// (this entry, oracle_intersect and oracle_occluded return trace_batch's refusal status too; the
+// Python binding raises it)
+int32_t oracle_trace(const ctl_scene_desc* desc, int64_t n, const ctl_ray* rays, int32_t mode, int32_t tie,
+                     float* out_t, float* out_u, float* out_v, uint32_t* out_tri, uint32_t* out_node, uint64_t* stats,
+                     int32_t threads) {
+    return trace_batch(desc, n, rays, mode, tie, out_t, out_u, out_v, out_tri, out_node, stats, threads, nullptr);
+}
+// oracle_trace with the per-ray stack depth and the refusal status of trace_batch
+int32_t oracle_trace_depth(const ctl_scene_desc* desc, int64_t n, const ctl_ray* rays, int32_t mode, int32_t tie,
+                           float* out_t, float* out_u, float* out_v, uint32_t* out_tri, uint32_t* out_node,
+                           uint64_t* stats, int32_t threads, int32_t* depth) {
+    return trace_batch(desc, n, rays, mode, tie, out_t, out_u, out_v, out_tri, out_node, stats, threads, depth);
+}
+// The largest traversal stack any query reached since the last reset, over
+// every entry (the render passes' own rays included).
+int32_t oracle_depth_peak() { return g_depth_peak.load(); }
+void oracle_depth_peak_reset() { g_depth_peak = 0; }
 
 // Occluded(Ray(o, d), 0, tmax) per ray (rays[i].tmax = tmax, tmin ignored): the
 // reference's closest-hit form (any_hit 0) or the any-hit query (any_hit 1)
 // with boxes culled at tmax - eps (cull 0, round 4's rule), at tmax (1), not
 // past the ray origin (2) or at tmax + slab_slack (3, the product's).
-void oracle_occluded(const ctl_scene_desc* desc, int64_t n, const ctl_ray* rays, uint8_t* out, int32_t any_hit,
-                     int32_t tie, int32_t cull, int32_t threads) {
+static int32_t occluded_batch(const ctl_scene_desc* desc, int64_t n, const ctl_ray* rays, uint8_t* out, int32_t any_hit,
+                              int32_t tie, int32_t cull, int32_t threads, int32_t* depth) {
     SceneView S{desc};
+    std::atomic<bool> refused{false};
     if (threads <= 0) threads = (int)std::thread::hardware_concurrency();
     std::atomic<int64_t> next{0};
     auto worker = [&]() {
@@ -1985,23 +2068,37 @@ void oracle_occluded(const ctl_scene_desc* desc, int64_t n, const ctl_ray* rays,
             const int64_t end = std::min<int64_t>(n, base + 256);
             for (int64_t i = base; i < end; i++) {
                 const ctl_ray& r = rays[i];
+                tl_depth.peak = 0;
+                tl_depth.refused = false;
                 out[i] = occluded_query(S, v3(r.o[0], r.o[1], r.o[2]), v3(r.d[0], r.d[1], r.d[2]), r.tmax, any_hit != 0,
                                         tie, cull, nullptr) ? 1 : 0;
+                if (depth) depth[i] = tl_depth.peak;
+                if (tl_depth.refused) refused = true;
             }
         }
     };
     std::vector<std::thread> ts;
     for (int i = 0; i < threads; i++) ts.emplace_back(worker);
     for (auto& t : ts) t.join();
+    return refused ? 1 : 0;
+}
+int32_t oracle_occluded(const ctl_scene_desc* desc, int64_t n, const ctl_ray* rays, uint8_t* out, int32_t any_hit,
+                        int32_t tie, int32_t cull, int32_t threads) {
+    return occluded_batch(desc, n, rays, out, any_hit, tie, cull, threads, nullptr);
+}
+// oracle_occluded with the per-ray stack depth and the refusal status (trace_batch)
+int32_t oracle_occluded_depth(const ctl_scene_desc* desc, int64_t n, const ctl_ray* rays, uint8_t* out, int32_t any_hit,
+                              int32_t tie, int32_t cull, int32_t threads, int32_t* depth) {
+    return occluded_batch(desc, n, rays, out, any_hit, tie, cull, threads, depth);
 }
 
 // Batch kernel output layout (ctl_hit), TraceHelper.cu:722-731.
-void oracle_intersect(const ctl_scene_desc* desc, int64_t n, const ctl_ray* rays, ctl_hit* hits, int32_t any_hit,
-                      int32_t tie, int32_t threads) {
+static int32_t intersect_batch(const ctl_scene_desc* desc, int64_t n, const ctl_ray* rays, ctl_hit* hits,
+                               int32_t any_hit, int32_t tie, int32_t threads, int32_t* depth) {
     std::vector<float> t(n), u(n), v(n);
     std::vector<uint32_t> tri(n), node(n);
-    oracle_trace(desc, n, rays, any_hit ? 2 : 1, tie, t.data(), u.data(), v.data(), tri.data(), node.data(), nullptr,
-                 threads);
+    const int32_t refused = trace_batch(desc, n, rays, any_hit ? 2 : 1, tie, t.data(), u.data(), v.data(), tri.data(),
+                                        node.data(), nullptr, threads, depth);
     for (int64_t i = 0; i < n; i++) {
         ctl_hit& h = hits[i];
         h.dist = t[i];
@@ -2012,6 +2109,16 @@ void oracle_intersect(const ctl_scene_desc* desc, int64_t n, const ctl_ray* rays
             h.bary = (int32_t)(((uint32_t)yd << 16) | (uint32_t)xd);
         }
     }
+    return refused;
+}
+int32_t oracle_intersect(const ctl_scene_desc* desc, int64_t n, const ctl_ray* rays, ctl_hit* hits, int32_t any_hit,
+                         int32_t tie, int32_t threads) {
+    return intersect_batch(desc, n, rays, hits, any_hit, tie, threads, nullptr);
+}
+// oracle_intersect with the per-ray stack depth and the refusal status (trace_batch)
+int32_t oracle_intersect_depth(const ctl_scene_desc* desc, int64_t n, const ctl_ray* rays, ctl_hit* hits,
+                               int32_t any_hit, int32_t tie, int32_t threads, int32_t* depth) {
+    return intersect_batch(desc, n, rays, hits, any_hit, tie, threads, depth);
 }
 
 // Closest hit by scanning every leaf entry of every node (BVH-independent truth).
@@ -2076,6 +2183,7 @@ void oracle_brute_force(const ctl_scene_desc* d, int64_t n, const ctl_ray* rays,
 static uint64_t render_pass(const ctl_scene_desc* desc, const ctl_pt_params* prm, uint64_t pass_index, ctl_pixel* fb,
                             int32_t tie, int32_t threads, uint32_t pixel_stride, uint64_t* stats, uint64_t* events) {
     if (shading_refusal(desc, "oracle_render_pass")) return UINT64_MAX;
+    g_stack_refused = false;
     const uint32_t nseq = 4096, len = 30;
     std::vector<float> s1((size_t)nseq * len), s2((size_t)nseq * len * 2);
     sampler_tables(pass_index, nseq, len, s1.data(), s2.data());
@@ -2131,6 +2239,7 @@ static uint64_t render_pass(const ctl_scene_desc* desc, const ctl_pt_params* prm
     std::vector<std::thread> tv;
     for (int i = 0; i < threads; i++) tv.emplace_back(worker);
     for (auto& t : tv) t.join();
+    if (g_stack_refused) return UINT64_MAX;   // a ray needed more than kStackMax stack entries: nothing added
     for (size_t i = 0; i < smp.size(); i++)
         if (smp[i].set && (!multi || lands_owned(v2(smp[i].x, smp[i].y)))) add_sample(fb, W, H, smp[i].x, smp[i].y, smp[i].L);
     if (stats) { stats[0] = totalRays; stats[1] = acc[0]; stats[2] = acc[1]; stats[3] = acc[2]; }
@@ -2211,6 +2320,7 @@ static float depth_d3d(float d, float n, float f) {   // DeviceDepthImage::Norma
 uint64_t oracle_prim_pass(const ctl_scene_desc* desc, const ctl_prim_params* prm, uint64_t pass_index, ctl_pixel* fb,
                           float* depth, int32_t tie, int32_t threads) {
     if (shading_refusal(desc, "oracle_prim_pass")) return UINT64_MAX;
+    g_stack_refused = false;
     // the delta bounce loop of the first_non_delta modes is not restated
     if (prm->draw_mode == CTL_PRIM_FIRST_NON_DELTA_LE || prm->draw_mode == CTL_PRIM_FIRST_NON_DELTA_F ||
         prm->draw_mode == CTL_PRIM_FIRST_NON_DELTA_F_DIRECT)
@@ -2307,6 +2417,7 @@ uint64_t oracle_prim_pass(const ctl_scene_desc* desc, const ctl_prim_params* prm
     std::vector<std::thread> tv;
     for (int i = 0; i < threads; i++) tv.emplace_back(worker);
     for (auto& t : tv) t.join();
+    if (g_stack_refused) return UINT64_MAX;
     for (uint32_t y = 0; y < H; y++)
         for (uint32_t x = 0; x < W; x++) add_sample(fb, W, H, (float)x, (float)y, out[(size_t)y * W + x]);
     return totalRays;
@@ -2338,7 +2449,10 @@ uint64_t oracle_wpt_render_pass(const ctl_scene_desc* desc, int32_t direct, int3
                                 int32_t rr_start_depth, uint32_t passes_done, uint64_t pass_index, ctl_pixel* fb,
                                 int32_t tie, int32_t threads) {
     if (shading_refusal(desc, "oracle_wpt_render_pass")) return UINT64_MAX;
-    return wpt_render(desc, direct != 0, max_path_length, rr_start_depth, passes_done, pass_index, fb, tie, threads);
+    g_stack_refused = false;
+    const uint64_t rays = wpt_render(desc, direct != 0, max_path_length, rr_start_depth, passes_done, pass_index, fb, tie,
+                                     threads);
+    return g_stack_refused ? UINT64_MAX : rays;   // refused: fb means nothing
 }
 
 // AnimatedMesh::k_ComputeState on caller-owned copies of the compiled arrays.
