@@ -42,7 +42,7 @@ __all__ = ["HostScene", "Tracer", "PathTracer", "BlockSampler", "BLOCK_INFO_DTYP
            "CTL_SCENE_HALF_HOST_QUIRK", "CTL_SCENE_BINARY_BVH", "CTL_PT_MEGAKERNEL", "CTL_PT_WAVEFRONT", "CTL_PT_RENDER_AHEAD", "lib", "diffuse_material",
            "MaterialExt", "BsdfQuery", "BsdfResult", "BSDF_QUERY_DTYPE", "BSDF_RESULT_DTYPE", "dielectric_material",
            "thindielectric_material", "conductor_material", "roughconductor_material", "plastic_material",
-           "fresnel_diffuse_reflectance", "host_bsdf_eval"]
+           "fresnel_diffuse_reflectance", "host_bsdf_eval", "host_math_eval", "MATH_FUNCTIONS"]
 
 
 def lib():
@@ -253,6 +253,31 @@ def host_bsdf_eval(desc, queries):
     out = np.zeros(q.shape[0], dtype=BSDF_RESULT_DTYPE)
     _check(lib().ctl_host_bsdf_eval(C.byref(desc), q.shape[0], q.ctypes.data, out.ctypes.data), None,
            "ctl_host_bsdf_eval")
+    return out
+
+
+MATH_FUNCTIONS = {name: i for i, name in enumerate(_abi.CTL_MATH_FUNCTIONS)}   # name -> CTL_MATH_* id
+
+
+def _math_fn(fn):
+    return MATH_FUNCTIONS[fn] if isinstance(fn, str) else int(fn)
+
+
+def host_math_eval(fn, a, b=None):
+    """The scalar arithmetic of the kernels on the CPU (ctl_host_math_eval): function `fn` (a name of
+    MATH_FUNCTIONS or its id) of the 32-bit words of `a` (float32, or uint32 bit patterns) and, for atan2,
+    pow and div, of `b`; returns uint32 result words, the device entry's arithmetic bit for bit.
+    normal_encode16 takes n x 3 floats, normal_decode16 returns n x 3 words."""
+    fn = _math_fn(fn)
+    a = np.ascontiguousarray(a)
+    assert a.dtype.itemsize == 4, a.dtype
+    n = a.size // 3 if fn == MATH_FUNCTIONS["normal_encode16"] else a.size
+    if b is not None:
+        b = np.ascontiguousarray(b)
+        assert b.dtype.itemsize == 4 and b.size == n, (b.dtype, b.size)
+    out = np.zeros((n, 3) if fn == MATH_FUNCTIONS["normal_decode16"] else n, dtype=np.uint32)
+    _check(lib().ctl_host_math_eval(fn, n, a.ctypes.data, b.ctypes.data if b is not None else None, out.ctypes.data),
+           None, "ctl_host_math_eval")
     return out
 
 
@@ -817,6 +842,13 @@ class Tracer:
         device memory (ctl_bsdf_eval); results to n ctl_bsdf_result records in device memory."""
         _check(self._L.ctl_bsdf_eval(self._ctx, int(n), int(queries_ptr), int(results_ptr), stream or None), self._ctx,
                "ctl_bsdf_eval")
+
+    def math_eval(self, fn, n, a_ptr, b_ptr, out_ptr, stream=0):
+        """The scalar arithmetic of the kernels for n elements in device memory (ctl_math_eval): `fn` as
+        host_math_eval's; a_ptr / b_ptr to 32-bit input words (b_ptr 0 for a one-argument function),
+        out_ptr to the uint32 result words."""
+        _check(self._L.ctl_math_eval(self._ctx, _math_fn(fn), int(n), int(a_ptr), int(b_ptr) or None, int(out_ptr),
+                                     stream or None), self._ctx, "ctl_math_eval")
 
     def rays_traced(self):
         return int(self._L.ctl_rays_traced(self._ctx))

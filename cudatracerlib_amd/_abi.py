@@ -33,6 +33,10 @@ CTL_ENULL, CTL_EDELTA_REFLECTION, CTL_EDELTA_TRANSMISSION = 0x1, 0x20, 0x40
 CTL_EALL = 0x1ff
 CTL_MEASURE_SOLID_ANGLE, CTL_MEASURE_DISCRETE = 1, 4
 CTL_BSDF_OP_SAMPLE, CTL_BSDF_OP_F, CTL_BSDF_OP_PDF = 0, 1, 2
+# ctl_math_eval / ctl_host_math_eval function ids
+CTL_MATH_FUNCTIONS = ["sin", "cos", "tan", "acos", "atan", "atan2", "exp", "log", "log2", "pow", "erf", "erfinv", "div",
+                      "sqrt", "rcp", "half_ieee", "half_quirk", "half_round_int", "u16_trunc", "normal_encode16",
+                      "normal_decode16"]
 CTL_MICROFACET_BECKMANN = 0
 CTL_MICROFACET_GGX = 1
 CTL_TEX_POINT, CTL_TEX_BILINEAR, CTL_TEX_EWA, CTL_TEX_TRILINEAR = 0, 1, 2, 3
@@ -298,6 +302,8 @@ SYMBOLS = [
     ("ctl_host_scene_set_mesh_material_ext", C.c_int32, [_vp, C.c_uint32, C.POINTER(MaterialExt), C.c_uint32]),
     ("ctl_host_bsdf_eval", C.c_int32, [C.POINTER(SceneDesc), C.c_uint64, _vp, _vp]),
     ("ctl_bsdf_eval", C.c_int32, [_vp, C.c_uint64, _vp, _vp, _vp]),
+    ("ctl_host_math_eval", C.c_int32, [C.c_uint32, C.c_uint64, _vp, _vp, _vp]),
+    ("ctl_math_eval", C.c_int32, [_vp, C.c_uint32, C.c_uint64, _vp, _vp, _vp, _vp]),
     ("ctl_host_scene_add_texture", C.c_int32, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp]),
     ("ctl_host_scene_add_node", C.c_int32, [_vp, C.c_uint32, _vp]),
     ("ctl_host_scene_add_area_light", C.c_int32, [_vp, C.c_uint32, C.c_uint32, _vp]),

@@ -4,10 +4,16 @@
 // Every function keeps the operation order of the reference
 // (Ilinite/CudaTracerLib Math/Vector.h, MathFunc.h, float4x4.h, Frame.h) and
 // the library is compiled with -ffp-contract=off, so the GPU results are bit
-// identical to the CPU oracle's.  Transcendentals are evaluated as
-// correctly-rounded fp32 through fp64: the
-// reference itself uses host libm on its CPU path and __sinf-class
-// intrinsics on its CUDA path (MathFunc.h:222-288), which disagree.
+// identical to the CPU oracle's.  Transcendentals are the fp32 rounding of the
+// fp64 library result, cr_f(x) = (float)f((double)x):
+// the reference itself uses host libm on its CPU path and __sinf-class
+// intrinsics on its CUDA path (MathFunc.h:222-288), which disagree.  That is
+// the correctly rounded fp32 at all but a few inputs where the second rounding
+// falls the wrong way (glibc 2.35: sin 2, cos 4, log 5, acos 2, atan 2 of all
+// float32 inputs; tan, exp, log2 none).  Host (libm) and device (the ROCm
+// device library) agree on every float32 input of the eight one-argument
+// functions; cr_pow and cr_atan2 differ at eight known inputs
+// (tests/test_gpu_cr_math.py, tests/golden/cr_hard_cases.json).
 #pragma once
 #include <stdint.h>
 #include <math.h>

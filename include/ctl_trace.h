@@ -54,7 +54,8 @@ extern "C" {
                                decode, ctl_tonemap_constants); BSDF types 3, 4, 6, 7, 8 (ctl_material_ext,
                                ctl_host_scene_set_mesh_material_ext, ctl_bsdf_eval, ctl_host_bsdf_eval) and
                                ctl_scene_desc.materials_ext appended as the desc's last member: a caller
-                               fills the desc it passes from this header (zero it first) */
+                               fills the desc it passes from this header (zero it first); the scalar
+                               arithmetic's batch entries (ctl_math_eval, ctl_host_math_eval) */
 
 #if defined(_WIN32)
 #define CTL_API __declspec(dllexport)
@@ -1214,6 +1215,31 @@ CTL_API ctl_status ctl_host_bsdf_eval(const ctl_scene_desc* desc, uint64_t n, co
  * d_results are device arrays of n records. */
 CTL_API ctl_status ctl_bsdf_eval(ctl_ctx* ctx, uint64_t n, const ctl_bsdf_query* d_queries,
                                  ctl_bsdf_result* d_results, void* stream);
+/* The scalar arithmetic under every kernel, for arrays of inputs: function fn
+ * of a[i] (and b[i] for the two-argument functions; b is ignored otherwise) to
+ * out[i], a 32-bit word holding the float's bits or the integer result.  The
+ * entries call the functions the kernels and the host scene compiler call
+ * (ctl_math.h, ctl_bsdf.h); no scene is needed.  For HALF_*, HALF_ROUND_INT
+ * and NORMAL_DECODE16 the integer input is the bit pattern of a[i].
+ * NORMAL_ENCODE16 reads a as n packed (x, y, z) triples; NORMAL_DECODE16
+ * writes three words (x, y, z) per element.  U16_TRUNC is defined on
+ * [0, 65536) and NaN only. */
+enum {
+    CTL_MATH_SIN = 0, CTL_MATH_COS = 1, CTL_MATH_TAN = 2, CTL_MATH_ACOS = 3, CTL_MATH_ATAN = 4,
+    CTL_MATH_ATAN2 = 5,            /* cr_atan2(a, b) */
+    CTL_MATH_EXP = 6, CTL_MATH_LOG = 7, CTL_MATH_LOG2 = 8,
+    CTL_MATH_POW = 9,              /* cr_pow(a, b) */
+    CTL_MATH_ERF = 10, CTL_MATH_ERFINV = 11,
+    CTL_MATH_DIV = 12,             /* fp32 a / b */
+    CTL_MATH_SQRT = 13, CTL_MATH_RCP = 14,
+    CTL_MATH_HALF_IEEE = 15, CTL_MATH_HALF_QUIRK = 16, CTL_MATH_HALF_ROUND_INT = 17, CTL_MATH_U16_TRUNC = 18,
+    CTL_MATH_NORMAL_ENCODE16 = 19, CTL_MATH_NORMAL_DECODE16 = 20,
+    CTL_MATH_COUNT = 21
+};
+CTL_API ctl_status ctl_host_math_eval(uint32_t fn, uint64_t n, const float* a, const float* b, uint32_t* out);
+/* The same on the device: d_a, d_b and d_out are device arrays. */
+CTL_API ctl_status ctl_math_eval(ctl_ctx* ctx, uint32_t fn, uint64_t n, const float* d_a, const float* d_b,
+                                 uint32_t* d_out, void* stream);
 CTL_API int32_t ctl_host_scene_add_animated_mesh(ctl_host_scene* s, const ctl_anim_vertex* vertices,
                                                  uint32_t n_vertices, const uint32_t* indices, uint32_t n_triangles,
                                                  const float* uvs, const uint8_t* mat_index,

@@ -32,10 +32,11 @@ static inline float o_copysign(float a, float b) {
 static inline float frac(float f) { return f - floorf(f); }                 // MathFunc.h:138-141
 static inline int floor2int(float v) { return (int)floorf(v); }            // MathFunc.h:143-145
 
-// Transcendentals: correctly-rounded fp32 obtained through fp64 evaluation.
-// The reference's own two paths already disagree here (host libm sinf vs
-// CUDA __sinf / sincosf, MathFunc.h:272-288); both the oracle and the HIP
-// kernels pin the correctly-rounded result so they agree bit for bit.
+// Transcendentals: the fp32 rounding of the fp64 library result (correctly
+// rounded at all but a few inputs).  The reference's own two
+// paths already disagree here (host libm sinf vs CUDA __sinf / sincosf,
+// MathFunc.h:272-288); the oracle and the HIP kernels both take this form,
+// and tests/test_gpu_cr_math.py holds the device library to the host's.
 static inline float cr_sin(float x) { return (float)std::sin((double)x); }
 static inline float cr_cos(float x) { return (float)std::cos((double)x); }
 static inline float cr_tan(float x) { return (float)std::tan((double)x); }
