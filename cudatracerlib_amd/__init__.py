@@ -853,6 +853,14 @@ class Tracer:
     def rays_traced(self):
         return int(self._L.ctl_rays_traced(self._ctx))
 
+    def tail_handovers(self):
+        """(lanes, breaks) of the persistent path kernels' tail hand-over since the last reset_rays
+        (ctl_tail_handovers): unfinished traversals carried over to a wave's next iteration, and the
+        trace loops left early to do so."""
+        lanes, breaks = C.c_uint64(0), C.c_uint64(0)
+        _check(self._L.ctl_tail_handovers(self._ctx, C.byref(lanes), C.byref(breaks)), self._ctx, "ctl_tail_handovers")
+        return int(lanes.value), int(breaks.value)
+
     def reset_rays(self, stream=0):
         _check(self._L.ctl_reset_rays(self._ctx, stream), self._ctx, "ctl_reset_rays")
 

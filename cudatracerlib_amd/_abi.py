@@ -274,6 +274,7 @@ SYMBOLS = [
     ("ctl_wpt_render_pass", C.c_int32, [_vp, C.POINTER(WptParams), _vp, _vp]),
     ("ctl_prim_pass", C.c_int32, [_vp, C.POINTER(PrimParams), _vp, _vp, _vp]),
     ("ctl_rays_traced", C.c_uint64, [_vp]),
+    ("ctl_tail_handovers", C.c_int32, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("ctl_reset_rays", C.c_int32, [_vp, _vp]),
     ("ctl_sync", C.c_int32, [_vp, _vp]),
     ("ctl_scene_stack_bound", C.c_int32, [_vp]),
@@ -361,6 +362,10 @@ SYMBOLS = [
                                           C.POINTER(C.c_float)]),
 ]
 
+# Added within CTL_ABI_VERSION 4: a library built from an earlier commit (a CTL_LIB base of the
+# tools/ab_*.sh comparisons) loads without them, and calling one there raises AttributeError.
+OPTIONAL = {"ctl_tail_handovers"}
+
 _lib = None
 
 
@@ -374,7 +379,12 @@ def load(path=LIB_PATH):
         raise RuntimeError(f"libctl_trace.so not built ({path}); run `python -c 'import __graft_entry__ as g; g.build()'`")
     lib = C.CDLL(path)
     for name, res, args in SYMBOLS:
-        fn = getattr(lib, name)
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:
+            if name in OPTIONAL:
+                continue
+            raise
         fn.restype = res
         fn.argtypes = args
     v = lib.ctl_abi_version()

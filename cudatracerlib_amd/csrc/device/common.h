@@ -112,6 +112,11 @@ __device__ __forceinline__ I wave_claim(I* cursor, uint64_t mask) {
     return base + (I)lanes_below(mask);
 }
 
+// Slots of ctl_ctx::d_counters (16 words) beside [0] rays, [1] overflow, [2..4] statistics and the
+// CTL_PROFILE_TRACE build's [5], [6], [8..14]: the tail hand-over's lanes handed over and trace loops
+// left early (persistent_loop.h; ctl_tail_handovers)
+constexpr int kTailHandovers = 7, kTailBreaks = 15;
+
 // End of a tracing kernel: the overflow flag and (STATS) the traversal statistics into counters[1..4]
 template <bool STATS>
 __device__ __forceinline__ void flush_counters(unsigned long long* counters, bool overflow, const TraceStats& ts) {
@@ -483,7 +488,7 @@ struct ctl_ctx {
     ctl::PinnedArray<float> h_s1[2], h_s2[2];
     ctl::Event ev[2];
     int next_buf = 0, active = -1;
-    unsigned long long* d_counters = nullptr;   // [0] rays [1] overflow [2..4] stats (fixed)
+    unsigned long long* d_counters = nullptr;   // [0] rays [1] overflow [2..4] stats [7], [15] tail hand-over (fixed)
     ctl::PinnedArray<unsigned long long> h_overflow;   // host copy of d_counters[1], read at ctl_sync
     bool overflow_seen = false;                 // sticky: a traversal stack overflowed since the last reset
     // 64-bit work cursors ([0] batch intersect [1] path pass [2] prim pass): resident

@@ -355,7 +355,12 @@ __global__ __launch_bounds__(kBlock) void path_kernel(DevScene S_arg, PathParams
 //    the Russian-roulette tail instead of idling until their longest path
 //    ends;
 //  * the traverser is local to an iteration: only the path variables and the
-//    pending ray are loop-carried, keeping the register peak low.
+//    pending ray are loop-carried, keeping the register peak low;
+//  * tail hand-over (one-instance kernels, CTL_TAIL_LANES): once a ray of the
+//    iteration has finished and only a few lanes still traverse, the wave leaves
+//    the trace; those lanes write their traversal state above their stack top
+//    and go on in the next iteration, beside the rays the others start meanwhile.
+//    A ray's visit order does not depend on where its rounds are cut.
 // Work items are independent (own sampler index, own sample slot), so the
 // framebuffer is bit-identical to path_kernel's.
 // The loop is persistent_loop.h, the body of two kernel templates so that the
@@ -1004,7 +1009,7 @@ static ctl_status render_pass_speculative(ctl_ctx* c, const ctl_pt_params* param
 CTL_API ctl_status ctl_render_pass(ctl_ctx* c, const ctl_pt_params* params, ctl_pixel* d_fb, void* stream) {
 #ifdef CTL_PROFILE_TRACE
     ctl_status r = launch_pass(c, params, d_fb, false, stream);
-    unsigned long long v[10];
+    unsigned long long v[11];
     if (hipStreamSynchronize(reinterpret_cast<hipStream_t>(stream)) == hipSuccess &&
         hipMemcpy(v, c->d_counters + 5, sizeof(v), hipMemcpyDeviceToHost) == hipSuccess) {
         fprintf(stderr, "[profile] trace/total wave time %.4f (%llu / %llu); inner loop: %llu wave iterations, "
@@ -1013,6 +1018,8 @@ CTL_API ctl_status ctl_render_pass(ctl_ctx* c, const ctl_pt_params* params, ctl_
                 (double)v[5] / (double)v[6]);
         fprintf(stderr, "[profile] lanes in the round per inner iteration %.1f; rounds %llu, lanes holding a leaf at the "
                         "leaf phase %.1f\n", (double)v[7] / (double)v[4], v[8], (double)v[9] / (double)v[8]);
+        fprintf(stderr, "[profile] tail hand-over: %llu lanes handed over at %llu breaks of the trace loop\n",
+                v[kTailHandovers - 5], v[kTailBreaks - 5]);
         (void)hipMemset(c->d_counters + 5, 0, sizeof(v));
     }
     return r;
@@ -1228,12 +1235,23 @@ CTL_API uint64_t ctl_rays_traced(ctl_ctx* c) {
     return v[0];
 }
 
+CTL_API ctl_status ctl_tail_handovers(ctl_ctx* c, uint64_t* lanes, uint64_t* breaks) {
+    if (!c) return CTL_ERR_INVALID;
+    unsigned long long v[16];
+    CTL_HIP(c, hipSetDevice(c->device));
+    CTL_HIP(c, hipDeviceSynchronize());
+    CTL_HIP(c, hipMemcpy(v, c->d_counters, sizeof(v), hipMemcpyDeviceToHost));
+    if (lanes) *lanes = v[kTailHandovers];
+    if (breaks) *breaks = v[kTailBreaks];
+    return CTL_OK;
+}
+
 CTL_API int32_t ctl_scene_stack_bound(const ctl_ctx* c) { return c && c->has_scene ? c->stack_bound : 0; }
 
 CTL_API ctl_status ctl_reset_rays(ctl_ctx* c, void* stream) {
     if (!c) return CTL_ERR_INVALID;
     CTL_HIP(c, hipSetDevice(c->device));
-    CTL_HIP(c, hipMemsetAsync(c->d_counters, 0, 8 * sizeof(unsigned long long), reinterpret_cast<hipStream_t>(stream)));
+    CTL_HIP(c, hipMemsetAsync(c->d_counters, 0, 16 * sizeof(unsigned long long), reinterpret_cast<hipStream_t>(stream)));
     c->overflow_seen = false;
     return CTL_OK;
 }

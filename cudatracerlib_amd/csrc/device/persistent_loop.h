@@ -18,7 +18,9 @@
     // the refill: the sample's landing code (all store_sample needs of the pixel) rides
     // in the top bits of the parked work item word (items < 2^kListItemBits, host).
     constexpr bool kList = std::is_same<OWN, OwnList>::value;
-    CTL_LANE_STACK(st);
+    // tail hand-over (traverse.h CTL_TAIL_LANES): the SINGLE kernels without statistics
+    constexpr bool kTail = SINGLE && !STATS && CTL_TAIL_LANES > 0;
+    CTL_LANE_STACK_REC(st, kTail ? kTailRecWords + 1 : 0);   // the record and the kept stack pointer
     SamplerDev rng{s1, s2, P.nseq, P.len, 0, 0, 0, 0};
     // work item of the lane's path (pass slot * PS.per_pass + item), parked in
     // LDS for the path's lifetime instead of holding a VGPR through the traces
@@ -32,6 +34,8 @@
     TraceStats ts{0, 0, 0};
     uint32_t rays = 0;
     bool active = false, exhausted = false, shadowPhase = false, ending = false, ok = true;
+    // kTail: the lane's pending ray is part-way through its traversal (record above its stack top)
+    bool susp = false;
 #ifdef CTL_PROFILE_TRACE
     long long prof_trace = 0;
     const long long prof_start = wall_clock64();
@@ -85,64 +89,109 @@
         }
         if (active) {
             HitRec h = no_hit((shadowPhase && shadowAny) ? sh.dist - S.ray_eps : FLT_MAX);
-            rays++;
+            if (!kTail || !susp) rays++;   // a handed-over ray was counted at its first call
 #ifdef CTL_PROFILE_TRACE
             const long long pc0 = wall_clock64();
 #endif
             if (S.n_nodes != 0) {
                 Traverser<2, STATS, SINGLE, WIDE, CTL_ALPHA_OF(FULL)> T;
                 T.anyhit = shadowPhase && shadowAny;
+                // a handed-over lane sets up the same ray by the same calls on the same
+                // inputs (the sentinel init pushes is the one already at the bottom; init
+                // also clears the overflow flag, which is why `ok` takes it after every call)
                 T.init(S, v.rori, shadowPhase ? sh.d : v.rdir, 0.0f, S.ray_eps, h.t, st, &ts,
                        T.anyhit ? sh.dist : -1.0f);
-                while (!T.done) T.round(S, st, &ts);
-                h = T.h;
+                if constexpr (kTail) {
+                    // ... then takes back its stack top and its record
+                    if (susp) { st.sp = st.kept_sp(); T.resume(st); }
+                    // Break rule.  `entered` lanes run this call; the lanes still in the
+                    // loop after a round vote (the ballot sees exactly them, so the
+                    // outcome is uniform among them and they leave together): hand over
+                    // once fewer than CTL_TAIL_LANES per 64 entered lanes still traverse.
+                    // Relative to `entered`, so the few lanes of a wave at the end of a
+                    // launch (entered * CTL_TAIL_LANES <= 64) are never cut.
+                    // Progress: (1) every call runs at least one round for every
+                    // unfinished lane before the first vote; (2) in >= 1, CTL_TAIL_LANES
+                    // < 64, so in * 64 < entered * CTL_TAIL_LANES implies in < entered: a
+                    // break happens only when a ray of this call has finished; (3) so
+                    // every iteration of the persistent loop finishes a ray or advances
+                    // every open traversal by a round, and a traversal is a finite
+                    // number of rounds: the loop ends as the loop without the rule does.
+                    const uint32_t entered = (uint32_t)__popcll(__ballot(1));
+                    for (;;) {
+                        T.round(S, st, &ts);
+                        if (T.done) break;
+                        const uint64_t inm = __ballot(1);
+                        const uint32_t in = (uint32_t)__popcll(inm);
+                        if (in * 64u < entered * (uint32_t)CTL_TAIL_LANES) {
+                            // counted here, one atomic pair per break: counts carried in
+                            // registers through the loop cost the FULL kernel 13 -> 38 spilled VGPRs
+                            if ((int)(threadIdx.x & 63) == __ffsll((unsigned long long)inm) - 1) {
+                                atomicAdd(&counters[kTailHandovers], (unsigned long long)in);
+                                atomicAdd(&counters[kTailBreaks], 1ull);
+                            }
+                            break;
+                        }
+                    }
+                    susp = !T.done;
+                    // sp goes to a private word of its own: nothing of the stack is live in shading
+                    if (susp) { T.suspend(st); st.keep_sp(); }
+                    else h = T.h;
+                } else {
+                    while (!T.done) T.round(S, st, &ts);
+                    h = T.h;
+                }
                 ok &= !st.overflow;
             }
 #ifdef CTL_PROFILE_TRACE
             prof_trace += wall_clock64() - pc0;
 #endif
-            // the FULL kernels read parked state where the shading uses it (Park's
-            // partial loads), the lean kernel all of it after the trace
-            constexpr bool lazy = FULL != kShadeLean;
-            if (lazy) park.load_core(v, rng);
-            else park.load(v, sh, rng);
-            bool cont;
-            if (shadowPhase) {
-                if (lazy) { v.cl = park.get3(0); sh.add = park.get3(16); }
-                if (!shadow_occluded(S, shadowAny, h, sh.dist)) v.cl = v.cl + sh.add;
-                shadowPhase = false;
-                cont = !ending && v.depth++ < P.max_path_length;
-                if (lazy && cont) { park.store_cl(v); park.store_depth(v); }
-            } else if (h.tri == 0xffffffffu) {
-                if (lazy) park.load(v, sh, rng);
-                v.cl = v.cl + env_miss<FULL>(S, P, v);   // PathTracer.cu:98-111
-                cont = false;
-            } else {
-                // the FULL kernel keeps the path's first-hit texture partials in its own
-                // sample slot (written only when the path ends), not in four VGPRs
-                // carried through every trace
-                float4* part = kList ? PS.s + ((uint32_t)*pkw & kListItemMask) : PS.s + *pkw;
-                ending = lazy ? !shade_hit<FULL, SINGLE, Park>(S, P, rng, v, h, sh, part, &park)
-                              : !shade_hit<FULL, SINGLE>(S, P, rng, v, h, sh, part);
-                shadowPhase = sh.valid;
-                cont = sh.valid || (!ending && v.depth++ < P.max_path_length);
-                if (lazy && cont) park.store_shaded(v, sh, rng);
-            }
-            if (!cont) {
-                if constexpr (kList) {
-                    const uint32_t wd = (uint32_t)*pkw;   // one pass per launch: the item is the slot
-                    store_sample_coded(PS, wd & kListItemMask, wd >> kListItemBits, mk3s(1.0f) * v.cl);
+            // a suspended lane skips all of the shading: its path state stays parked, its
+            // pending ray in the registers that hold it (v.rori, v.rdir / sh.d, sh.dist, shadowPhase)
+            if (!kTail || !susp) {
+                // the FULL kernels read parked state where the shading uses it (Park's
+                // partial loads), the lean kernel all of it after the trace
+                constexpr bool lazy = FULL != kShadeLean;
+                if (lazy) park.load_core(v, rng);
+                else park.load(v, sh, rng);
+                bool cont;
+                if (shadowPhase) {
+                    if (lazy) { v.cl = park.get3(0); sh.add = park.get3(16); }
+                    if (!shadow_occluded(S, shadowAny, h, sh.dist)) v.cl = v.cl + sh.add;
+                    shadowPhase = false;
+                    cont = !ending && v.depth++ < P.max_path_length;
+                    if (lazy && cont) { park.store_cl(v); park.store_depth(v); }
+                } else if (h.tri == 0xffffffffu) {
+                    if (lazy) park.load(v, sh, rng);
+                    v.cl = v.cl + env_miss<FULL>(S, P, v);   // PathTracer.cu:98-111
+                    cont = false;
                 } else {
-                    uint32_t px, py, ps, kk;
-                    split((uint32_t)*pkw, ps, kk);
-                    const PathParams& Pw = FULL ? *opaque_ptr(&P) : P;   // as at the refill
-                    OWN::work_pixel(Pw, own_tbl, kk, px, py);
-                    if (lazy) park.load_px(v);
-                    store_sample(Pw, PS, ps, kk, px, py, v.pX, mk3s(1.0f) * v.cl);
+                    // the FULL kernel keeps the path's first-hit texture partials in its own
+                    // sample slot (written only when the path ends), not in four VGPRs
+                    // carried through every trace
+                    float4* part = kList ? PS.s + ((uint32_t)*pkw & kListItemMask) : PS.s + *pkw;
+                    ending = lazy ? !shade_hit<FULL, SINGLE, Park>(S, P, rng, v, h, sh, part, &park)
+                                  : !shade_hit<FULL, SINGLE>(S, P, rng, v, h, sh, part);
+                    shadowPhase = sh.valid;
+                    cont = sh.valid || (!ending && v.depth++ < P.max_path_length);
+                    if (lazy && cont) park.store_shaded(v, sh, rng);
                 }
-                active = false;
-            } else if (!lazy) {
-                park.store(v, sh, rng);
+                if (!cont) {
+                    if constexpr (kList) {
+                        const uint32_t wd = (uint32_t)*pkw;   // one pass per launch: the item is the slot
+                        store_sample_coded(PS, wd & kListItemMask, wd >> kListItemBits, mk3s(1.0f) * v.cl);
+                    } else {
+                        uint32_t px, py, ps, kk;
+                        split((uint32_t)*pkw, ps, kk);
+                        const PathParams& Pw = FULL ? *opaque_ptr(&P) : P;   // as at the refill
+                        OWN::work_pixel(Pw, own_tbl, kk, px, py);
+                        if (lazy) park.load_px(v);
+                        store_sample(Pw, PS, ps, kk, px, py, v.pX, mk3s(1.0f) * v.cl);
+                    }
+                    active = false;
+                } else if (!lazy) {
+                    park.store(v, sh, rng);
+                }
             }
         }
     }

@@ -52,6 +52,19 @@ constexpr int kStackMax = 128;
 #define CTL_LEAF_BREAK 3
 #endif
 
+// Tail hand-over of the SINGLE persistent path kernels (persistent_loop.h): a
+// wave leaves its trace loop once a ray of the call has finished and fewer than
+// CTL_TAIL_LANES of every 64 lanes that entered the call still traverse; those
+// lanes write their resumable state above their stack top (LaneStack::rec_put,
+// Traverser4::suspend) and go on in the next iteration (resume), beside the
+// rays the finished lanes start meanwhile.  0 compiles the loop without it.
+#ifndef CTL_TAIL_LANES
+#define CTL_TAIL_LANES 12
+#endif
+static_assert(CTL_TAIL_LANES >= 0 && CTL_TAIL_LANES < 64, "a break needs a finished lane: threshold below the wave size");
+// words of a suspended SINGLE traversal: nodeAddr, leafAddr, h.t, h.u, h.v, h.tri, tcull
+constexpr int kTailRecWords = 7;
+
 // Per-ray visit order (round 4).  Every traversal is a function of its ray
 // alone, never of the other rays of its wave:
 //  * binary trees (CTL_SCENE_BINARY_BVH, stats launches) run the reference's
@@ -192,14 +205,34 @@ struct LaneStack {
         if (sp >= kLdsStack) v = sp < kStackMax ? spill[sp - kLdsStack] : CTL_SENTINEL;
         return v;
     }
+    // Word w of a suspended traversal's record (kTailRecWords words): the slots
+    // right above the stack top, addressed as push addresses them (LDS, then the
+    // private array), without moving sp.  The record is not a traversal entry:
+    // it may lie past kStackMax, in the words CTL_LANE_STACK_REC adds to the
+    // private array (an overflowed stack, sp > kStackMax, keeps it in there).
+    __device__ __forceinline__ void rec_put(int w, int v) {
+        const int s = min(sp, kStackMax) + w;
+        if (s < kLdsStack) ctl_lds_stack[s * kStackBlock + tid] = v;
+        else spill[s - kLdsStack] = v;
+    }
+    // sp of a suspended traversal, in the private word behind the record's room
+    __device__ __forceinline__ void keep_sp() { spill[kStackMax - kLdsStack + kTailRecWords] = sp; }
+    __device__ __forceinline__ int kept_sp() const { return spill[kStackMax - kLdsStack + kTailRecWords]; }
+    __device__ __forceinline__ int rec_get(int w) const {
+        const int s = min(sp, kStackMax) + w;
+        if (s < kLdsStack) return ctl_lds_stack[s * kStackBlock + tid];
+        return spill[s - kLdsStack];
+    }
 };
-#define CTL_LANE_STACK(name)                       \
-    int name##_spill[kStackMax - kLdsStack];       \
-    LaneStack name;                                \
-    name.spill = name##_spill;                     \
-    name.sp = 0;                                   \
-    name.tid = (int)threadIdx.x;                   \
+// REC: words above the kStackMax entries for a suspension record and its sp (0 or kTailRecWords + 1)
+#define CTL_LANE_STACK_REC(name, REC)                  \
+    int name##_spill[kStackMax - kLdsStack + (REC)];   \
+    LaneStack name;                                    \
+    name.spill = name##_spill;                         \
+    name.sp = 0;                                       \
+    name.tid = (int)threadIdx.x;                       \
     name.overflow = false
+#define CTL_LANE_STACK(name) CTL_LANE_STACK_REC(name, 0)
 constexpr size_t kStackLdsBytes = sizeof(int) * kLdsStack * kStackBlock;
 // path_kernel_persistent keeps one word per thread after the stacks (the work
 // item of the lane's path); the tail/balance experiments' areas follow it
@@ -327,6 +360,37 @@ struct Traverser4 {
             else { leafAddr = 0; nodeAddr = WIDE ? 0 : S.start_node; }
         }
         if (any_query() && anyDist >= 0.0f) tcull = anyDist + slab_slack(cur, S.cull_m);
+    }
+
+    // Tail hand-over (SINGLE, between two rounds of an unfinished traversal).
+    // What a round reads and init does not derive from the scene and the ray is
+    // nodeAddr, leafAddr, the hit so far and tcull: suspend writes them above
+    // the lane's stack top, whose entries stay as they are (sp: LaneStack::keep_sp).  h.node is
+    // the one instance wherever a triangle is held; resumeLeaves is only ever
+    // set at the instance level, and `anyhit` is the caller's to set, as for init.
+    __device__ __forceinline__ void suspend(LaneStack& st) const {
+        static_assert(SINGLE, "only the one-level traversal is handed over");
+        st.rec_put(0, nodeAddr);
+        st.rec_put(1, leafAddr);
+        st.rec_put(2, __float_as_int(h.t));
+        st.rec_put(3, __float_as_int(h.u));
+        st.rec_put(4, __float_as_int(h.v));
+        st.rec_put(5, (int)h.tri);
+        st.rec_put(6, __float_as_int(tcull));
+    }
+    // After an init with the arguments of the one that began the traversal (the
+    // ray's constants come from the same calls on the same inputs, bit for bit)
+    // and with the caller's sp put back: the record read back.
+    __device__ __forceinline__ void resume(const LaneStack& st) {
+        static_assert(SINGLE && !STATS, "only the one-level traversal is handed over");
+        nodeAddr = st.rec_get(0);
+        leafAddr = st.rec_get(1);
+        h.t = __int_as_float(st.rec_get(2));
+        h.u = __int_as_float(st.rec_get(3));
+        h.v = __int_as_float(st.rec_get(4));
+        h.tri = (uint32_t)st.rec_get(5);
+        h.node = h.tri == 0xffffffffu ? 0xffffffffu : instIdx;
+        tcull = __int_as_float(st.rec_get(6));   // an any-hit query's is init's value, unchanged
     }
 
     // TriangleData UV set 0 at (u, v) -> Material::AlphaTest (TraceHelper.cu:140-152)

@@ -1053,7 +1053,12 @@ CTL_API ctl_status ctl_block_sampler_passes_done(const ctl_block_sampler* s, uin
  * batched rays) since the last reset; 64-bit (the reference's counter is a
  * 32-bit atomicInc, Base/Platform.cu:12-21).  Synchronises the device. */
 CTL_API uint64_t ctl_rays_traced(ctl_ctx* ctx);
-/* Zeroes the ray counter and clears a recorded traversal stack overflow. */
+/* Tail hand-over of the one-instance persistent path kernels since the last
+ * reset: lanes whose unfinished traversal a wave carried over to its next
+ * iteration, and the trace loops left early to do so (either may be NULL).
+ * Diagnostic only: results do not depend on it.  Synchronises the device. */
+CTL_API ctl_status ctl_tail_handovers(ctl_ctx* ctx, uint64_t* lanes, uint64_t* breaks);
+/* Zeroes the ray counter (and the hand-over counts) and clears a recorded traversal stack overflow. */
 CTL_API ctl_status ctl_reset_rays(ctl_ctx* ctx, void* stream);
 /* The ABI's sync point (the reference's cudaDeviceSynchronize after a pass,
  * Tracer.h:240, TraceHelper.cu:744): waits for the stream, then returns
