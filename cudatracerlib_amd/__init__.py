@@ -42,7 +42,8 @@ __all__ = ["HostScene", "Tracer", "PathTracer", "BlockSampler", "BLOCK_INFO_DTYP
            "CTL_SCENE_HALF_HOST_QUIRK", "CTL_SCENE_BINARY_BVH", "CTL_PT_MEGAKERNEL", "CTL_PT_WAVEFRONT", "CTL_PT_RENDER_AHEAD", "lib", "diffuse_material",
            "MaterialExt", "BsdfQuery", "BsdfResult", "BSDF_QUERY_DTYPE", "BSDF_RESULT_DTYPE", "dielectric_material",
            "thindielectric_material", "conductor_material", "roughconductor_material", "plastic_material",
-           "fresnel_diffuse_reflectance", "host_bsdf_eval", "host_math_eval", "MATH_FUNCTIONS"]
+           "fresnel_diffuse_reflectance", "host_bsdf_eval", "host_math_eval", "MATH_FUNCTIONS",
+           "LIGHT_QUERY_DTYPE", "LIGHT_RESULT_DTYPE", "host_light_eval"]
 
 
 def lib():
@@ -253,6 +254,21 @@ def host_bsdf_eval(desc, queries):
     out = np.zeros(q.shape[0], dtype=BSDF_RESULT_DTYPE)
     _check(lib().ctl_host_bsdf_eval(C.byref(desc), q.shape[0], q.ctypes.data, out.ctypes.data), None,
            "ctl_host_bsdf_eval")
+    return out
+
+
+LIGHT_QUERY_DTYPE = np.dtype([("light", "<u4"), ("ref", "<f4", 3), ("ref_n", "<f4", 3), ("sample", "<f4", 2)])
+LIGHT_RESULT_DTYPE = np.dtype([("value", "<f4", 3), ("pdf", "<f4"), ("d", "<f4", 3), ("dist", "<f4"), ("p", "<f4", 3),
+                               ("measure", "<u4"), ("n", "<f4", 3), ("pad", "<u4")])
+
+
+def host_light_eval(desc, queries):
+    """Light::sampleDirect of desc's lights for an array of LIGHT_QUERY_DTYPE queries, on the CPU
+    (ctl_host_light_eval): LIGHT_RESULT_DTYPE results, the device entry's arithmetic bit for bit."""
+    q = np.ascontiguousarray(queries, dtype=LIGHT_QUERY_DTYPE)
+    out = np.zeros(q.shape[0], dtype=LIGHT_RESULT_DTYPE)
+    _check(lib().ctl_host_light_eval(C.byref(desc), q.ctypes.data, q.shape[0], out.ctypes.data), None,
+           "ctl_host_light_eval")
     return out
 
 
@@ -513,6 +529,36 @@ class HostScene:
         r = self._L.ctl_host_scene_add_area_light(self._h, node, local_material, arr)
         if r < 0:
             _check(1, None, "add_area_light")
+        return r
+
+    def add_point_light(self, pos, intensity):
+        """PointLight(pos, intensity); returns its light index in the next compile (delta lights follow
+        the area lights and the environment, in the order they were added)."""
+        f3 = C.c_float * 3
+        r = self._L.ctl_host_scene_add_point_light(self._h, f3(*pos), f3(*intensity))
+        if r < 0:
+            _check(1, None, "add_point_light")
+        return r
+
+    def add_spot_light(self, pos, target, intensity, cutoff_deg, beam_deg):
+        """SpotLight(pos, target, intensity, width=cutoff_deg, fall=beam_deg): full intensity inside the
+        beam width, a linear-in-angle fall to zero at the cutoff angle; returns its light index."""
+        f3 = C.c_float * 3
+        r = self._L.ctl_host_scene_add_spot_light(self._h, f3(*pos), f3(*target), f3(*intensity), float(cutoff_deg),
+                                                  float(beam_deg))
+        if r < 0:
+            _check(1, None, "add_spot_light")
+        return r
+
+    def add_distant_light(self, irradiance, direction, scene_radius):
+        """DistantLight(irradiance, direction.normalized(), scene_radius): the light travels along
+        `direction`.  As in the reference, its disk is centred at direction * 1.1 * scene_radius about
+        the origin, and only points on or beyond the disk's plane are lit (INTEGRATION.md, section 2a);
+        returns its light index."""
+        f3 = C.c_float * 3
+        r = self._L.ctl_host_scene_add_distant_light(self._h, f3(*irradiance), f3(*direction), float(scene_radius))
+        if r < 0:
+            _check(1, None, "add_distant_light")
         return r
 
     def set_camera(self, pos, target, up, fov_deg, width, height, near=1.0, far=100000.0):
@@ -836,6 +882,12 @@ class Tracer:
         wbase = self.read_array(_abi.CTL_ARRAY_MESH_WIDE_BASE, 0, wbase0.size, np.uint32, 1).reshape(-1)
         scene = self.read_array(_abi.CTL_ARRAY_SCENE_WIDE_BVH, 0, scene0.shape[0], np.float32, 32)
         return mesh, wbase, scene
+
+    def light_eval(self, n, queries_ptr, results_ptr, stream=0):
+        """Light::sampleDirect of the uploaded scene's lights for n ctl_light_query records in device
+        memory (ctl_light_eval); results to n ctl_light_result records in device memory."""
+        _check(self._L.ctl_light_eval(self._ctx, int(queries_ptr), int(n), int(results_ptr), stream or None), self._ctx,
+               "ctl_light_eval")
 
     def bsdf_eval(self, n, queries_ptr, results_ptr, stream=0):
         """BSDFALL::sample / f / pdf of the uploaded scene's materials for n ctl_bsdf_query records in

@@ -139,6 +139,22 @@ class Light(C.Structure):
 
 CTL_LIGHT_DIFFUSE = 0
 CTL_LIGHT_INFINITE = 1
+CTL_LIGHT_POINT, CTL_LIGHT_SPOT, CTL_LIGHT_DISTANT = 2, 3, 4
+
+
+class LightParams(C.Structure):      # ctl_light_params: a delta light's light_tris slot, 64 B
+    _fields_ = [("pos", C.c_float * 3), ("s", C.c_float * 3), ("t", C.c_float * 3), ("n", C.c_float * 3),
+                ("cos_beam_width", C.c_float), ("cos_cutoff_angle", C.c_float), ("cutoff_angle", C.c_float),
+                ("inv_transition_width", C.c_float)]
+
+
+class LightQuery(C.Structure):       # ctl_light_query, 36 B
+    _fields_ = [("light", C.c_uint32), ("ref", C.c_float * 3), ("ref_n", C.c_float * 3), ("sample", C.c_float * 2)]
+
+
+class LightResult(C.Structure):      # ctl_light_result, 64 B
+    _fields_ = [("value", C.c_float * 3), ("pdf", C.c_float), ("d", C.c_float * 3), ("dist", C.c_float),
+                ("p", C.c_float * 3), ("measure", C.c_uint32), ("n", C.c_float * 3), ("pad", C.c_uint32)]
 
 
 class EnvLight(C.Structure):          # ctl_env_light (InfiniteLight), 112 B
@@ -308,6 +324,11 @@ SYMBOLS = [
     ("ctl_host_scene_add_texture", C.c_int32, [_vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _vp, _vp]),
     ("ctl_host_scene_add_node", C.c_int32, [_vp, C.c_uint32, _vp]),
     ("ctl_host_scene_add_area_light", C.c_int32, [_vp, C.c_uint32, C.c_uint32, _vp]),
+    ("ctl_host_scene_add_point_light", C.c_int32, [_vp, _vp, _vp]),
+    ("ctl_host_scene_add_spot_light", C.c_int32, [_vp, _vp, _vp, _vp, C.c_float, C.c_float]),
+    ("ctl_host_scene_add_distant_light", C.c_int32, [_vp, _vp, _vp, C.c_float]),
+    ("ctl_host_light_eval", C.c_int32, [C.POINTER(SceneDesc), _vp, C.c_int64, _vp]),
+    ("ctl_light_eval", C.c_int32, [_vp, _vp, C.c_int64, _vp, _vp]),
     ("ctl_host_scene_set_camera", C.c_int32, [_vp, _vp, _vp, _vp, C.c_float, C.c_float, C.c_float,
                                               C.c_uint32, C.c_uint32]),
     ("ctl_host_scene_set_flags", C.c_int32, [_vp, C.c_uint32]),

@@ -13,6 +13,7 @@
 #include "dispatch.h"
 #include "traverse.h"
 #include "../ctl_env.h"
+#include "../ctl_light.h"
 
 namespace ctl {
 
@@ -475,6 +476,8 @@ struct ctl_ctx {
     bool has_scene = false;
     bool half_quirk = false;
     bool has_delta = false;                     // some uploaded material has a delta lobe (prim.hip)
+    uint32_t material_level = 0;                // shading level the materials and the environment ask for
+    bool has_delta_light = false;               // some uploaded light is a point, spot or distant light
     uint32_t nseq = 4096, len = 30;
     ctl::DevPool fixed;                         // owns the arrays allocated once by ctl_create
     float* d_s1[2] = {nullptr, nullptr};        // (fixed)

@@ -77,8 +77,17 @@ ctl_status validate(ctl_ctx* c, const ctl_scene_desc* d, uint32_t dirty) {
     if (dirty & (CTL_DIRTY_LIGHTS | CTL_DIRTY_ENV)) {
         for (uint32_t i = 0; i < d->n_lights; i++) {
             if (d->lights[i].orthogonal) { c->err = "scene_upload: orthogonal DiffuseLight unsupported"; return CTL_ERR_INVALID; }
-            if (d->lights[i].kind > CTL_LIGHT_INFINITE || (d->lights[i].kind == CTL_LIGHT_INFINITE) != (i == d->env_map_index)) {
+            if (d->lights[i].kind > CTL_LIGHT_DISTANT) {
+                c->err = "scene_upload: light " + std::to_string(i) + ": unknown kind " + std::to_string(d->lights[i].kind);
+                return CTL_ERR_INVALID;
+            }
+            if ((d->lights[i].kind == CTL_LIGHT_INFINITE) != (i == d->env_map_index)) {
                 c->err = "scene_upload: the environment light must be the light env_map_index names";
+                return CTL_ERR_INVALID;
+            }
+            const char* why = light_is_delta(d->lights[i].kind) ? delta_light_check(d->lights[i], d->light_tris, d->n_light_tris) : nullptr;
+            if (why) {
+                c->err = "scene_upload: light " + std::to_string(i) + ": " + why;
                 return CTL_ERR_INVALID;
             }
         }
@@ -507,7 +516,16 @@ ctl_status commit_arrays(ctl_ctx* c, const ctl_scene_desc* d, uint32_t dirty, hi
             if (bsdf_ext_type(d->materials[i].bsdf_type)) S.full_shading = kShadeMat;
             if (d->materials[i].combined_type & kEDelta) c->has_delta = true;
         }
+        c->material_level = S.full_shading;
     }
+    // a point, spot or distant light runs the level of its own (shading.h); every
+    // other scene keeps the level its materials and environment ask for
+    if (dirty & CTL_DIRTY_LIGHTS) {
+        c->has_delta_light = false;
+        for (uint32_t i = 0; i < d->n_lights; i++)
+            if (light_is_delta(d->lights[i].kind)) c->has_delta_light = true;
+    }
+    S.full_shading = c->has_delta_light ? (uint32_t)kShadeLights : c->material_level;
     if (dirty & (CTL_DIRTY_NODES | CTL_DIRTY_MESHES | CTL_DIRTY_BVH)) {
         S.n_nodes = d->n_nodes;
         S.start_node = d->scene_start_node;
@@ -562,6 +580,8 @@ void free_scene(ctl_ctx* c) {
     c->h_meshes.clear();
     c->has_scene = false;
     c->has_delta = false;
+    c->material_level = kShadeLean;
+    c->has_delta_light = false;
     c->h_wbase.clear();
     c->tree_flags = 0xffffffffu;
     c->device_eps = false;

@@ -71,26 +71,31 @@ __device__ __forceinline__ f2 primary_ray(const DevScene& S, SamplerDev& rng, ui
 // mat = env plus the dielectric, thindielectric, conductor, roughconductor and plastic BSDFs (ctl_bsdf.h): a scene
 // with one of those types runs this level, every other scene the instantiations it ran before, whose code the five
 // types do not touch.
-enum : int { kShadeLean = 0, kShadeFull = 1, kShadeEnv = 2, kShadeAlpha = 3, kShadeMat = 4 };
+// lights = mat plus the point, spot and distant lights (ctl_light.h) in the light sample: a scene that holds one of
+// them runs this level, every other scene the instantiations it ran before.
+enum : int { kShadeLean = 0, kShadeFull = 1, kShadeEnv = 2, kShadeAlpha = 3, kShadeMat = 4, kShadeLights = 5 };
 // the traversal's ALPHA flag of a shading level
-#define CTL_ALPHA_OF(F) ((F) == kShadeEnv || (F) == kShadeAlpha || (F) == kShadeMat)
-// levels that carry the environment light, and the seven-type BSDF dispatch
-#define CTL_ENV_OF(F) ((F) == kShadeEnv || (F) == kShadeMat)
-#define CTL_EXT_OF(F) ((F) == kShadeMat)
+#define CTL_ALPHA_OF(F) ((F) == kShadeEnv || (F) == kShadeAlpha || (F) == kShadeMat || (F) == kShadeLights)
+// levels that carry the environment light, the seven-type BSDF dispatch, and the delta lights
+#define CTL_ENV_OF(F) ((F) == kShadeEnv || (F) == kShadeMat || (F) == kShadeLights)
+#define CTL_EXT_OF(F) ((F) == kShadeMat || (F) == kShadeLights)
+#define CTL_DELTA_LIGHTS_OF(F) ((F) == kShadeLights)
 // kernels that never trace (wavefront shade, WPT iterate) share the full instantiation
 #define CTL_NO_TRACE_LEVEL(F) ((F) == kShadeAlpha ? kShadeFull : (F))
 // Host: f(FU) with DevScene::full_shading as a constant (dispatch.h), over the
-// five levels or, for the kernels that never trace, the four they instantiate.
-// full_shading only ever holds one of the five (scene_dev.hip).
+// six levels or, for the kernels that never trace, the five they instantiate.
+// full_shading only ever holds one of the six (scene_dev.hip).
 template <class F>
 void with_shade_level(uint32_t full, F&& f) {
-    const bool known = with_level<kShadeLean, kShadeFull, kShadeEnv, kShadeAlpha, kShadeMat>((int)full, f);
+    const bool known =
+        with_level<kShadeLean, kShadeFull, kShadeEnv, kShadeAlpha, kShadeMat, kShadeLights>((int)full, f);
     assert(known);
     (void)known;
 }
 template <class F>
 void with_no_trace_level(uint32_t full, F&& f) {
-    const bool known = with_level<kShadeLean, kShadeFull, kShadeEnv, kShadeMat>((int)CTL_NO_TRACE_LEVEL(full), f);
+    const bool known =
+        with_level<kShadeLean, kShadeFull, kShadeEnv, kShadeMat, kShadeLights>((int)CTL_NO_TRACE_LEVEL(full), f);
     assert(known);
     (void)known;
 }
@@ -157,12 +162,11 @@ __device__ __forceinline__ uint32_t sample_emitter(const DevScene& S, f2& sample
     return idx;
 }
 
-// Light::sampleDirect dispatch: the environment map or a diffuse area light
+// Light::sampleDirect dispatch (ctl_light.h): the kinds the level carries, else a diffuse area light
 template <int FULL>
 __device__ __forceinline__ spec sample_light_direct(const DevScene& S, uint32_t lidx, direct_rec& dRec, f2 sample) {
-    return CTL_ENV_OF(FULL) && S.lights[lidx].kind == CTL_LIGHT_INFINITE
-               ? env_sample_direct(env_view(S), dRec, sample)
-               : light_sample_direct(S.lights[lidx], S.light_tris, S.light_tri_cdf, dRec, sample);
+    return light_sample_direct_any<CTL_ENV_OF(FULL), CTL_DELTA_LIGHTS_OF(FULL)>(S.lights, S.light_tris, S.light_tri_cdf,
+                                                                                env_view(S), lidx, dRec, sample);
 }
 
 // The emitter of a hit whose material has one (mat.node_light_index set): index, record, and

@@ -119,7 +119,7 @@ struct DevScene {
     const float4* scene_wbvh;    // instance-level wide nodes
     const uint32_t* mesh_wbase;  // first wide node of each mesh
     uint32_t wide;               // wide trees present (scene flag CTL_SCENE_BINARY_BVH clear)
-    uint32_t full_shading;       // shading level of the path kernels: kShadeLean .. kShadeMat
+    uint32_t full_shading;       // shading level of the path kernels: kShadeLean .. kShadeLights
     uint32_t alpha;              // KernelDynamicScene::doAlphaMapping (some material has an alpha map)
     uint32_t s_wnode_base;
     uint32_t quant;              // wide trees in the 64-B quantized format (ctl_qnode.h)

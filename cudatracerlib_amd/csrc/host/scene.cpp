@@ -9,6 +9,7 @@
 //   getKernelSceneData eps            (Engine/DynamicScene.cpp:587)
 #include "scene.h"
 #include "../ctl_env.h"
+#include "../ctl_light.h"
 #include "bvh_build.h"
 #include "ref_split.h"
 #include "../ctl_shade.h"
@@ -16,6 +17,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <cstring>
 #include <mutex>
 #include <thread>
@@ -108,10 +110,29 @@ bool scene_add_light(ctl_host_scene* s, uint32_t node, uint32_t local_mat, const
         perNode += l.node == node;
     }
     if (perNode >= 2) { set_host_error("area light: MAX_AREALIGHT_NUM (2) lights per node"); return false; }
-    if (s->lights.size() >= CTL_MAX_NUM_LIGHTS) { set_host_error("area light: MAX_NUM_LIGHTS (16)"); return false; }
+    if (s->lights.size() + s->delta_lights.size() >= CTL_MAX_NUM_LIGHTS) { set_host_error("area light: MAX_NUM_LIGHTS (16)"); return false; }
     s->lights.push_back(ctl_host_scene::Light{node, local_mat, {L[0], L[1], L[2]}});
     return true;
 }
+
+namespace {
+bool finite3(const float v[3]) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
+
+// A point, spot or distant light joins the scene: its index among the lights of the next compile
+// (area lights, the environment, then these in order), or -1 past MAX_NUM_LIGHTS.
+int32_t scene_add_delta_light(ctl_host_scene* s, uint32_t kind, const float emit[3], const ctl_light_params& P,
+                              const char* who) {
+    const size_t before = s->lights.size() + (s->env_texture != 0xffffffffu ? 1 : 0) + s->delta_lights.size();
+    if (before >= CTL_MAX_NUM_LIGHTS) { set_host_error(std::string(who) + ": MAX_NUM_LIGHTS (16)"); return -1; }
+    ctl_host_scene::DeltaLight dl{};
+    dl.rec.radiance[0] = emit[0]; dl.rec.radiance[1] = emit[1]; dl.rec.radiance[2] = emit[2];
+    dl.rec.node_idx = 0xffffffffu;
+    dl.rec.kind = kind;
+    dl.params = P;
+    s->delta_lights.push_back(dl);
+    return (int32_t)before;
+}
+}  // namespace
 
 }  // namespace ctl
 
@@ -215,6 +236,40 @@ CTL_API int32_t ctl_host_scene_add_area_light(ctl_host_scene* s, uint32_t node, 
     for (size_t i = 0; i < s->lights.size(); i++)
         if (s->lights[i].node == node && s->lights[i].local_mat == local_material) return (int32_t)i;
     return -1;
+}
+
+CTL_API int32_t ctl_host_scene_add_point_light(ctl_host_scene* s, const float pos[3], const float intensity[3]) {
+    if (!s || !pos || !intensity) { set_host_error("add_point_light: null argument"); return -1; }
+    if (!finite3(pos) || !finite3(intensity)) { set_host_error("add_point_light: non-finite argument"); return -1; }
+    ctl_light_params P{};
+    P.pos[0] = pos[0]; P.pos[1] = pos[1]; P.pos[2] = pos[2];
+    return scene_add_delta_light(s, CTL_LIGHT_POINT, intensity, P, "add_point_light");
+}
+
+CTL_API int32_t ctl_host_scene_add_spot_light(ctl_host_scene* s, const float pos[3], const float target[3],
+                                              const float intensity[3], float cutoff_deg, float beam_deg) {
+    if (!s || !pos || !target || !intensity) { set_host_error("add_spot_light: null argument"); return -1; }
+    if (!finite3(pos) || !finite3(target) || !finite3(intensity) || !std::isfinite(cutoff_deg) || !std::isfinite(beam_deg)) {
+        set_host_error("add_spot_light: non-finite argument");
+        return -1;
+    }
+    const f3 p = mk3(pos[0], pos[1], pos[2]), t = mk3(target[0], target[1], target[2]);
+    if (!(length(t - p) > 0.0f)) { set_host_error("add_spot_light: target equals pos"); return -1; }
+    if (beam_deg > cutoff_deg) { set_host_error("add_spot_light: the beam width exceeds the cutoff angle"); return -1; }
+    return scene_add_delta_light(s, CTL_LIGHT_SPOT, intensity, spot_params(p, t, cutoff_deg, beam_deg), "add_spot_light");
+}
+
+CTL_API int32_t ctl_host_scene_add_distant_light(ctl_host_scene* s, const float irradiance[3], const float dir[3],
+                                                 float scene_radius) {
+    if (!s || !irradiance || !dir) { set_host_error("add_distant_light: null argument"); return -1; }
+    if (!finite3(irradiance) || !finite3(dir) || !std::isfinite(scene_radius)) {
+        set_host_error("add_distant_light: non-finite argument");
+        return -1;
+    }
+    const f3 d = mk3(dir[0], dir[1], dir[2]);
+    if (!(length(d) > 0.0f)) { set_host_error("add_distant_light: zero direction"); return -1; }
+    return scene_add_delta_light(s, CTL_LIGHT_DISTANT, irradiance, distant_params(normalize(d), scene_radius),
+                                 "add_distant_light");
 }
 
 CTL_API ctl_status ctl_host_scene_set_camera(ctl_host_scene* s, const float pos[3], const float target[3],
@@ -681,6 +736,18 @@ CTL_API ctl_status ctl_host_scene_compile(ctl_host_scene* s, uint32_t threads, c
         kl.kind = CTL_LIGHT_INFINITE;
         kl.node_idx = 0xffffffffu;
         envIndex = (uint32_t)s->klights.size();
+        s->klights.push_back(kl);
+    }
+    // the point, spot and distant lights, in the order they were added: each owns one
+    // light_tris slot after the area lights' triangles (ctl_light_params)
+    if (s->klights.size() + s->delta_lights.size() > CTL_MAX_NUM_LIGHTS) { set_host_error("compile: more than 16 lights"); return CTL_ERR_INVALID; }
+    for (const auto& dl : s->delta_lights) {
+        ctl_light kl = dl.rec;
+        kl.tri_first = (uint32_t)s->light_tris.size();
+        ctl_light_tri slot;
+        static_assert(sizeof(slot) == sizeof(dl.params), "slot size");
+        memcpy(&slot, &dl.params, sizeof(slot));
+        s->light_tris.push_back(slot);
         s->klights.push_back(kl);
     }
 

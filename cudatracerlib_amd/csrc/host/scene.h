@@ -49,6 +49,10 @@ struct ctl_host_scene {
     std::vector<Mesh> meshes;
     std::vector<Node> nodes;
     std::vector<Light> lights;
+    // point, spot and distant lights in the order they were added: the record (kind, radiance) and
+    // its ctl_light_params slot, which compile() places after the area lights' triangles
+    struct DeltaLight { ctl_light rec; ctl_light_params params; };
+    std::vector<DeltaLight> delta_lights;
     bool has_camera = false;
     float cam_pos[3], cam_tar[3], cam_up[3], cam_fov, cam_near, cam_far;
     uint32_t cam_w = 0, cam_h = 0;

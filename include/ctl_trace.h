@@ -55,7 +55,10 @@ extern "C" {
                                ctl_host_scene_set_mesh_material_ext, ctl_bsdf_eval, ctl_host_bsdf_eval) and
                                ctl_scene_desc.materials_ext appended as the desc's last member: a caller
                                fills the desc it passes from this header (zero it first); the scalar
-                               arithmetic's batch entries (ctl_math_eval, ctl_host_math_eval) */
+                               arithmetic's batch entries (ctl_math_eval, ctl_host_math_eval); the light
+                               kinds 2-4 (CTL_LIGHT_POINT / SPOT / DISTANT, ctl_light_params in a
+                               light_tris slot, record sizes unchanged), ctl_host_scene_add_point_light /
+                               _spot_light / _distant_light, ctl_light_eval, ctl_host_light_eval */
 
 #if defined(_WIN32)
 #define CTL_API __declspec(dllexport)
@@ -277,10 +280,37 @@ typedef struct {
     float sum_area;              /* ShapeSet::sumArea                            */
     uint32_t node_idx;           /* m_uNodeIdx                                   */
     uint32_t kind;               /* CTL_LIGHT_DIFFUSE, or CTL_LIGHT_INFINITE: the
-                                    environment (desc.env; other fields unused) */
+                                    environment (desc.env; other fields unused),
+                                    or a delta light (below)                     */
     uint32_t pad[2];
 } ctl_light;
-enum { CTL_LIGHT_DIFFUSE = 0, CTL_LIGHT_INFINITE = 1 };
+enum { CTL_LIGHT_DIFFUSE = 0, CTL_LIGHT_INFINITE = 1, CTL_LIGHT_POINT = 2, CTL_LIGHT_SPOT = 3, CTL_LIGHT_DISTANT = 4 };
+
+/* The delta lights reuse the record (PointLight, SpotLight, DistantLight,
+ * SceneTypes/Light.h:34-94, 145-292):
+ *   radiance   m_intensity (point, spot) or m_normalIrradiance (distant)
+ *   node_idx   0xFFFFFFFF: the light belongs to no node
+ *   tri_count  0
+ *   tri_first  ONE 64-byte slot of light_tris that the light owns, read as the
+ *              16 floats of ctl_light_params; cdf_first, sum_area unused (0).
+ * A path never hits them (eval = 0, pdfDirect = 1 in the discrete measure):
+ * they are reached through the light sample of the integrators only.
+ * ctl_scene_set_transform and ctl_scene_animate recompute the ShapeSets of
+ * diffuse lights and leave these slots alone; moving or recolouring a delta
+ * light is a ctl_scene_update with CTL_DIRTY_LIGHTS (no tree work).  Upload
+ * refuses a slot outside light_tris, non-finite values (+inf is allowed in
+ * inv_transition_width: equal spot angles), |n| != 1 beyond 1e-5, and a spot
+ * with cos_cutoff_angle > cos_beam_width. */
+typedef struct {
+    float pos[3];                /* lightPos (point), Position (spot); distant: 0  */
+    float s[3], t[3], n[3];      /* Frame ToWorld: spot Frame((Target-Position)
+                                    .normalized()), distant Frame(d); point: 0     */
+    float cos_beam_width;        /* spot: m_cosBeamWidth; distant: radius (the
+                                    constructor's r * 1.1f)                        */
+    float cos_cutoff_angle;      /* spot: m_cosCutoffAngle                         */
+    float cutoff_angle;          /* spot: m_cutoffAngle (radians)                  */
+    float inv_transition_width;  /* spot: 1 / (m_cutoffAngle - m_beamWidth)        */
+} ctl_light_params;              /* 64 B = sizeof(ctl_light_tri); unused floats 0  */
 
 /* InfiniteLight (SceneTypes/Light.h:294-367, Light.cpp:10-58): a latitude-
  * longitude radiance map around the scene.  The radiance map is an image
@@ -1151,6 +1181,27 @@ CTL_API int32_t ctl_host_scene_add_node(ctl_host_scene* s, uint32_t mesh, const 
  * instances (give each lit instance a mesh of its own). */
 CTL_API int32_t ctl_host_scene_add_area_light(ctl_host_scene* s, uint32_t node, uint32_t local_material,
                                               const float radiance[3]);
+/* The delta lights (ctl_light_params).  ctl_host_scene_compile appends them
+ * after the area lights and the environment, in the order they were added,
+ * each with its slot after the area lights' triangles; light_cdf stays uniform
+ * over all lights.  Each returns the light's index in that order (valid once no
+ * further area light or environment is added), or -1 with
+ * ctl_host_last_error: a 17th light, a non-finite number, target == pos, a
+ * zero dir, beam_deg > cutoff_deg.
+ *   point:   PointLight(pos, intensity).
+ *   spot:    SpotLight(pos, target, intensity, width = cutoff_deg, fall =
+ *            beam_deg) (Light.cu:268-277); equal angles are legal (the
+ *            loader's sun: 90 / 90).
+ *   distant: DistantLight(irradiance, dir.normalized(), scene_radius): the light
+ *            travels along dir.  The reference's sampleDirect (Light.cu:223-244)
+ *            centres the disk at dir * 1.1 * scene_radius about the origin and
+ *            lights only the points on or beyond its plane (dot(ref, dir) >=
+ *            1.1 * scene_radius); this is kept. */
+CTL_API int32_t ctl_host_scene_add_point_light(ctl_host_scene* s, const float pos[3], const float intensity[3]);
+CTL_API int32_t ctl_host_scene_add_spot_light(ctl_host_scene* s, const float pos[3], const float target[3],
+                                              const float intensity[3], float cutoff_deg, float beam_deg);
+CTL_API int32_t ctl_host_scene_add_distant_light(ctl_host_scene* s, const float irradiance[3], const float dir[3],
+                                                 float scene_radius);
 /* PerspectiveSensor: position, target, up, fov (degrees), near/far, resolution. */
 CTL_API ctl_status ctl_host_scene_set_camera(ctl_host_scene* s, const float pos[3], const float target[3],
                                              const float up[3], float fov_deg, float near_clip,
@@ -1220,6 +1271,34 @@ CTL_API ctl_status ctl_host_bsdf_eval(const ctl_scene_desc* desc, uint64_t n, co
  * d_results are device arrays of n records. */
 CTL_API ctl_status ctl_bsdf_eval(ctl_ctx* ctx, uint64_t n, const ctl_bsdf_query* d_queries,
                                  ctl_bsdf_result* d_results, void* stream);
+/* Light::sampleDirect of light `light` of the scene for a reference point `ref`
+ * with normal `ref_n` (DirectSamplingRecord(ref, ref_n)), through the dispatch
+ * the integrators' light sample uses, for all five kinds.  A query naming a
+ * light the scene does not have: zero value, measure all ones. */
+typedef struct {
+    uint32_t light;
+    float ref[3];
+    float ref_n[3];
+    float sample[2];
+} ctl_light_query;         /* 36 B */
+typedef struct {
+    float value[3];        /* the returned Spectrum                                   */
+    float pdf;             /* dRec.pdf                                                */
+    float d[3];            /* dRec.d                                                  */
+    float dist;            /* dRec.dist                                               */
+    float p[3];            /* dRec.p                                                  */
+    uint32_t measure;      /* dRec.measure: 1 solid angle, 3 area, 4 discrete         */
+    float n[3];            /* dRec.n                                                  */
+    uint32_t pad;
+} ctl_light_result;        /* 64 B */
+/* On the device, for the uploaded scene: d_queries and d_results are device
+ * arrays of n records. */
+CTL_API ctl_status ctl_light_eval(ctl_ctx* ctx, const ctl_light_query* d_queries, int64_t n,
+                                  ctl_light_result* d_results, void* stream);
+/* The same for a scene description, on the CPU (no GPU needed): the arithmetic
+ * of ctl_light_eval bit for bit. */
+CTL_API ctl_status ctl_host_light_eval(const ctl_scene_desc* desc, const ctl_light_query* queries, int64_t n,
+                                       ctl_light_result* results);
 /* The scalar arithmetic under every kernel, for arrays of inputs: function fn
  * of a[i] (and b[i] for the two-argument functions; b is ignored otherwise) to
  * out[i], a 32-bit word holding the float's bits or the integer result.  The
