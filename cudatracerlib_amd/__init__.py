@@ -43,7 +43,8 @@ __all__ = ["HostScene", "Tracer", "PathTracer", "BlockSampler", "BLOCK_INFO_DTYP
            "MaterialExt", "BsdfQuery", "BsdfResult", "BSDF_QUERY_DTYPE", "BSDF_RESULT_DTYPE", "dielectric_material",
            "thindielectric_material", "conductor_material", "roughconductor_material", "plastic_material",
            "fresnel_diffuse_reflectance", "host_bsdf_eval", "host_math_eval", "MATH_FUNCTIONS",
-           "LIGHT_QUERY_DTYPE", "LIGHT_RESULT_DTYPE", "host_light_eval"]
+           "LIGHT_QUERY_DTYPE", "LIGHT_RESULT_DTYPE", "host_light_eval",
+           "MEDIUM_QUERY_DTYPE", "MEDIUM_RESULT_DTYPE", "host_medium_eval"]
 
 
 def lib():
@@ -269,6 +270,25 @@ def host_light_eval(desc, queries):
     out = np.zeros(q.shape[0], dtype=LIGHT_RESULT_DTYPE)
     _check(lib().ctl_host_light_eval(C.byref(desc), q.ctypes.data, q.shape[0], out.ctypes.data), None,
            "ctl_host_light_eval")
+    return out
+
+
+MEDIUM_QUERY_DTYPE = np.dtype([("op", "<u4"), ("ori", "<f4", 3), ("dir", "<f4", 3), ("wo", "<f4", 3), ("tmin", "<f4"),
+                               ("tmax", "<f4"), ("u", "<f4", 2)])
+MEDIUM_RESULT_DTYPE = np.dtype([("hit", "<u4"), ("t0", "<f4"), ("t1", "<f4"), ("t", "<f4"), ("p", "<f4", 3),
+                                ("transmittance", "<f4", 3), ("sigma_a", "<f4", 3), ("sigma_s", "<f4", 3),
+                                ("pdf_success", "<f4"), ("pdf_success_rev", "<f4"), ("pdf_failure", "<f4"),
+                                ("value", "<f4"), ("pdf", "<f4"), ("wo_out", "<f4", 3)])
+
+
+def host_medium_eval(desc, queries):
+    """The medium's five operations (_abi.CTL_MEDIUM_*) of desc's volume for an array of
+    MEDIUM_QUERY_DTYPE queries, on the CPU (ctl_host_medium_eval): MEDIUM_RESULT_DTYPE results, the
+    device entry's arithmetic bit for bit."""
+    q = np.ascontiguousarray(queries, dtype=MEDIUM_QUERY_DTYPE)
+    out = np.zeros(q.shape[0], dtype=MEDIUM_RESULT_DTYPE)
+    _check(lib().ctl_host_medium_eval(C.byref(desc), q.ctypes.data, q.shape[0], out.ctypes.data), None,
+           "ctl_host_medium_eval")
     return out
 
 
@@ -559,6 +579,21 @@ class HostScene:
         r = self._L.ctl_host_scene_add_distant_light(self._h, f3(*irradiance), f3(*direction), float(scene_radius))
         if r < 0:
             _check(1, None, "add_distant_light")
+        return r
+
+    def add_homogeneous_volume(self, to_world, sigma_a, sigma_s, phase="isotropic", g=0.0, le=(0, 0, 0)):
+        """HomogeneousVolumeDensity(phase function, to_world, sigma_a, sigma_s, le): a medium filling the
+        unit cube transformed by the row-major 4x4 `to_world`; phase is "isotropic" or "hg" (Henyey-Greenstein
+        with |g| < 1).  A scene holds one volume at most; returns its index (0)."""
+        phases = {"isotropic": _abi.CTL_PHASE_ISOTROPIC, "hg": _abi.CTL_PHASE_HG}
+        if phase not in phases:
+            raise ValueError(f"add_homogeneous_volume: phase must be one of {sorted(phases)}")
+        f3 = C.c_float * 3
+        m = (C.c_float * 16)(*np.asarray(to_world, dtype=np.float32).reshape(16))
+        r = self._L.ctl_host_scene_add_homogeneous_volume(self._h, m, f3(*sigma_a), f3(*sigma_s), f3(*le),
+                                                          phases[phase], float(g))
+        if r < 0:
+            _check(1, None, "add_homogeneous_volume")
         return r
 
     def set_camera(self, pos, target, up, fov_deg, width, height, near=1.0, far=100000.0):
@@ -888,6 +923,12 @@ class Tracer:
         memory (ctl_light_eval); results to n ctl_light_result records in device memory."""
         _check(self._L.ctl_light_eval(self._ctx, int(queries_ptr), int(n), int(results_ptr), stream or None), self._ctx,
                "ctl_light_eval")
+
+    def medium_eval(self, n, queries_ptr, results_ptr, stream=0):
+        """The medium's five operations of the uploaded scene's volume for n ctl_medium_query records in
+        device memory (ctl_medium_eval); results to n ctl_medium_result records in device memory."""
+        _check(self._L.ctl_medium_eval(self._ctx, int(queries_ptr), int(n), int(results_ptr), stream or None), self._ctx,
+               "ctl_medium_eval")
 
     def bsdf_eval(self, n, queries_ptr, results_ptr, stream=0):
         """BSDFALL::sample / f / pdf of the uploaded scene's materials for n ctl_bsdf_query records in

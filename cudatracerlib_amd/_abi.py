@@ -48,7 +48,7 @@ CTL_PT_RENDER_AHEAD = 4
 # ctl_scene_update dirty groups (DynamicScene streams)
 CTL_DIRTY_TRI_DATA, CTL_DIRTY_WOOP, CTL_DIRTY_BVH, CTL_DIRTY_TRI_INDICES = 1, 2, 4, 8
 CTL_DIRTY_MATERIALS, CTL_DIRTY_MESHES, CTL_DIRTY_NODES, CTL_DIRTY_LIGHTS = 16, 32, 64, 128
-CTL_DIRTY_TEXTURES, CTL_DIRTY_ENV, CTL_DIRTY_ALL = 256, 512, 1023
+CTL_DIRTY_TEXTURES, CTL_DIRTY_ENV, CTL_DIRTY_VOLUMES, CTL_DIRTY_ALL = 256, 512, 1024, 2047
 # ctl_scene_read arrays
 (CTL_ARRAY_TRI_DATA, CTL_ARRAY_WOOP, CTL_ARRAY_BVH_NODES, CTL_ARRAY_SCENE_BVH, CTL_ARRAY_MESH_BOXES, CTL_ARRAY_RAY_EPS,
  CTL_ARRAY_SAMPLES_1D, CTL_ARRAY_SAMPLES_2D, CTL_ARRAY_NODE_XF, CTL_ARRAY_NODE_INV_XF, CTL_ARRAY_LIGHTS,
@@ -180,6 +180,31 @@ class AnimMesh(C.Structure):
                 ("tri_first", C.c_uint32), ("tri_count", C.c_uint32), ("max_bone", C.c_uint32)]
 
 
+CTL_MAX_NUM_VOLUMES = 16
+CTL_VOLUME_HOMOGENEOUS = 1
+CTL_PHASE_ISOTROPIC, CTL_PHASE_HG = 0, 1
+(CTL_MEDIUM_INTERSECT, CTL_MEDIUM_TRANSMITTANCE, CTL_MEDIUM_SAMPLE_DISTANCE, CTL_MEDIUM_PHASE_EVAL,
+ CTL_MEDIUM_PHASE_SAMPLE) = range(5)
+
+
+class Volume(C.Structure):           # ctl_volume (HomogeneousVolumeDensity + its phase function), 176 B
+    _fields_ = [("kind", C.c_uint32), ("phase", C.c_uint32), ("phase_g", C.c_float), ("sig_a", C.c_float * 3),
+                ("sig_s", C.c_float * 3), ("le", C.c_float * 3), ("volume_to_world", Float4x4),
+                ("world_to_volume", Float4x4)]
+
+
+class MediumQuery(C.Structure):      # ctl_medium_query, 56 B
+    _fields_ = [("op", C.c_uint32), ("ori", C.c_float * 3), ("dir", C.c_float * 3), ("wo", C.c_float * 3),
+                ("tmin", C.c_float), ("tmax", C.c_float), ("u", C.c_float * 2)]
+
+
+class MediumResult(C.Structure):     # ctl_medium_result, 96 B
+    _fields_ = [("hit", C.c_uint32), ("t0", C.c_float), ("t1", C.c_float), ("t", C.c_float), ("p", C.c_float * 3),
+                ("transmittance", C.c_float * 3), ("sigma_a", C.c_float * 3), ("sigma_s", C.c_float * 3),
+                ("pdf_success", C.c_float), ("pdf_success_rev", C.c_float), ("pdf_failure", C.c_float),
+                ("value", C.c_float), ("pdf", C.c_float), ("wo_out", C.c_float * 3)]
+
+
 class SceneDesc(C.Structure):
     _fields_ = [
         ("tri_data", C.POINTER(TriangleData)), ("n_tri_data", C.c_uint64),
@@ -209,6 +234,7 @@ class SceneDesc(C.Structure):
         ("anim_vertices", C.POINTER(AnimVertex)), ("n_anim_vertices", C.c_uint32),
         ("anim_triangles", C.POINTER(C.c_uint32)), ("n_anim_triangles", C.c_uint32),
         ("anim_meshes", C.POINTER(AnimMesh)), ("n_anim_meshes", C.c_uint32),
+        ("volumes", C.POINTER(Volume)), ("n_volumes", C.c_uint32),
         ("materials_ext", C.POINTER(MaterialExt)),
     ]
 
@@ -328,6 +354,9 @@ SYMBOLS = [
     ("ctl_host_scene_add_spot_light", C.c_int32, [_vp, _vp, _vp, _vp, C.c_float, C.c_float]),
     ("ctl_host_scene_add_distant_light", C.c_int32, [_vp, _vp, _vp, C.c_float]),
     ("ctl_host_light_eval", C.c_int32, [C.POINTER(SceneDesc), _vp, C.c_int64, _vp]),
+    ("ctl_host_scene_add_homogeneous_volume", C.c_int32, [_vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_float]),
+    ("ctl_host_medium_eval", C.c_int32, [C.POINTER(SceneDesc), _vp, C.c_int64, _vp]),
+    ("ctl_medium_eval", C.c_int32, [_vp, _vp, C.c_int64, _vp, _vp]),
     ("ctl_light_eval", C.c_int32, [_vp, _vp, C.c_int64, _vp, _vp]),
     ("ctl_host_scene_set_camera", C.c_int32, [_vp, _vp, _vp, _vp, C.c_float, C.c_float, C.c_float,
                                               C.c_uint32, C.c_uint32]),

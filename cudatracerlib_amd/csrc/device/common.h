@@ -14,6 +14,7 @@
 #include "traverse.h"
 #include "../ctl_env.h"
 #include "../ctl_light.h"
+#include "../ctl_medium.h"
 
 namespace ctl {
 
@@ -449,6 +450,13 @@ struct MeshRegion {
 
 // Device arrays of an uploaded scene (scene_dev.hip): one allocation per
 // KernelDynamicScene stream, reused by ctl_scene_update while it fits.
+// SA_LIGHTS is allocated whole at its first upload and never grows: CTL_MAX_NUM_LIGHTS ctl_light slots,
+// then the scene's ctl_volume at byte kVolumeAt (traverse.h scene_volume reads it there, ctl_ctx::d_volume
+// points at it).  Its `bytes` counts the uploaded lights only.  Whoever re-puts or resizes SA_LIGHTS keeps
+// the tail: scene_dev.hip commit_arrays writes the record back after every lights upload.
+constexpr size_t kVolumeAt = CTL_MAX_NUM_LIGHTS * sizeof(ctl_light);
+constexpr size_t kLightsArrayBytes = kVolumeAt + sizeof(ctl_volume);
+static_assert(kVolumeAt % 16 == 0, "the volume record is read at a 16-byte aligned address behind the light slots");
 enum SceneArr : int {
     SA_BVH, SA_WOOP, SA_IDX, SA_TRI, SA_MATS, SA_MESHES, SA_NODES, SA_SBVH, SA_XF, SA_IXF, SA_LIGHTS, SA_LTRIS,
     SA_LCDF, SA_LUT, SA_TEX, SA_TEXDATA, SA_ENV, SA_ENVDATA, SA_WBVH, SA_SWBVH, SA_WBASE, SA_MATX,
@@ -478,6 +486,8 @@ struct ctl_ctx {
     bool has_delta = false;                     // some uploaded material has a delta lobe (prim.hip)
     uint32_t material_level = 0;                // shading level the materials and the environment ask for
     bool has_delta_light = false;               // some uploaded light is a point, spot or distant light
+    ctl_volume h_volume{};                      // host copy of that record (all zero without one)
+    const ctl_volume* d_volume = nullptr;       // the uploaded scene's medium (behind the light slots of SA_LIGHTS), null without one
     uint32_t nseq = 4096, len = 30;
     ctl::DevPool fixed;                         // owns the arrays allocated once by ctl_create
     float* d_s1[2] = {nullptr, nullptr};        // (fixed)

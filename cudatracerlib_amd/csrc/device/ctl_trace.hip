@@ -163,16 +163,29 @@ struct PathCtx {
 
     // one iteration of `while (depth++ < MaxPathLength)`; false = path done
     __device__ __forceinline__ bool bounce() {
-        if (!(v.depth++ < P.max_path_length)) return false;
+        if (!(v.depth++ < P.max_path_length)) {
+            // kShadeMedia: the loop ends with r2 still the miss a medium interaction went on from
+            if constexpr (CTL_MEDIA_OF(FULL)) { if (v.vol_miss) v.cl = v.cl + env_miss<FULL>(S, P, v); }
+            return false;
+        }
         HitRec r2 = no_hit(FLT_MAX);   // traceRay (TraceHelper.cu:174-180)
         rays++;
         ok &= trace_one<0, STATS, SINGLE, WIDE, CTL_ALPHA_OF(FULL)>(S, v.rori, v.rdir, 0.0f, S.ray_eps, r2, st, &ts);
-        if (r2.tri == 0xffffffffu) {
-            v.cl = v.cl + env_miss<FULL>(S, P, v);   // PathTracer.cu:98-111
-            return false;
-        }
         ShadowReq sh;
-        const bool cont = shade_hit<FULL, SINGLE>(S, P, rng, v, r2, sh);
+        int ev = kMediumNone;
+        if constexpr (CTL_MEDIA_OF(FULL)) {
+            ev = medium_step<FULL>(S, P, rng, v, r2, sh);   // PathTracer.cu:24-58
+            if (ev != kMediumNone) v.vol_miss = r2.tri == 0xffffffffu;
+        }
+        bool cont = ev == kMediumScattered;
+        if (ev == kMediumNone) {
+            if (r2.tri == 0xffffffffu) {
+                v.cl = v.cl + env_miss<FULL>(S, P, v);   // PathTracer.cu:98-111
+                return false;
+            }
+            if constexpr (CTL_MEDIA_OF(FULL)) v.vol_miss = false;
+            cont = shade_hit<FULL, SINGLE>(S, P, rng, v, r2, sh);
+        }
         if (sh.valid) {
             const bool any = P.shadow_any_hit != 0;
             HitRec h = no_hit(any ? sh.dist - S.ray_eps : FLT_MAX);
@@ -182,6 +195,7 @@ struct PathCtx {
             else ok &= trace_one<0, STATS, SINGLE, WIDE, CTL_ALPHA_OF(FULL)>(S, v.rori, sh.d, 0.0f, S.ray_eps, h, st, &ts);
             if (!shadow_occluded(S, any, h, sh.dist)) v.cl = v.cl + sh.add;
         }
+        if constexpr (CTL_MEDIA_OF(FULL)) { if (ev == kMediumEnded && v.vol_miss) v.cl = v.cl + env_miss<FULL>(S, P, v); }
         return cont;
     }
 };
@@ -530,6 +544,19 @@ __global__ __launch_bounds__(kBlock) void occluded_kernel(DevScene S_arg, int64_
 
 }  // namespace
 
+// path_media.hip compiles the kernel templates above a second time, for the kShadeMedia level
+// alone: that level's kernels live in a code object of their own, and this file's is what it was
+// before the level existed (with them here, ten kernels of the levels full, env and alpha changed
+// their spills: the inliner's and the interprocedural passes' choices depend on a module's callers)
+#ifndef CTL_PATH_KERNELS_ONLY
+namespace ctl {
+void media_launch_path(ctl_ctx* c, bool persistent, bool stats, const PathParams& P, const float* s1, const float2* s2,
+                       uint64_t threads, uint64_t want, dim3 grid, unsigned long long* cursor, ctl_pixel* fb, SampleSlots PS,
+                       uint32_t tbl, hipStream_t s);
+void media_launch_blocks(ctl_ctx* c, const PathParams& P, const float* s1, const float2* s2, uint64_t items, uint64_t want,
+                         unsigned long long* cursor, SampleSlots PS, const uint32_t* own_tbl, hipStream_t s);
+}  // namespace ctl
+
 // ===========================================================================
 // Context + C ABI
 // ===========================================================================
@@ -791,8 +818,13 @@ static ctl_status launch_schedule(ctl_ctx* c, const ctl_pt_params* p, const Path
 #ifndef CTL_PERSIST_BPC
 #define CTL_PERSIST_BPC 0   // resident blocks per CU of the persistent path kernel (0: occupancy limit)
 #endif
+    if (CTL_MEDIA_OF((int)c->scene.full_shading)) {
+        ctl::media_launch_path(c, persistent, stats, P, s1, s2, threads, want, grid, cursor, fb, PS, tbl, s);
+        CTL_HIP(c, hipGetLastError());
+        return CTL_OK;
+    }
     with_tree(stats, c->scene.single != 0, c->scene.wide != 0, [&](auto ST, auto SG, auto WD) {
-        with_shade_level(c->scene.full_shading, [&](auto FU) {
+        with_traced_level_here(c->scene.full_shading, [&](auto FU) {
             if (persistent) {
                 constexpr size_t lds = persistent_lds_bytes();
                 auto k = path_kernel_persistent<decltype(ST)::value, decltype(SG)::value, decltype(WD)::value,
@@ -1154,8 +1186,11 @@ CTL_API ctl_status ctl_render_pass_blocks(ctl_ctx* c, const ctl_pt_params* p, co
     const SampleSlots PS = make_slots(c->d_slices.get(), (uint32_t)items);
     const float* s1 = c->d_s1[c->active];
     const float2* s2 = c->d_s2[c->active];
+    if (CTL_MEDIA_OF((int)c->scene.full_shading))
+        ctl::media_launch_blocks(c, P, s1, s2, items, want, cursor, PS, (const uint32_t*)c->d_block_tbl.get(), s);
+    else
     with_tree(c->scene.single != 0, c->scene.wide != 0, [&](auto SG, auto WD) {
-        with_shade_level(c->scene.full_shading, [&](auto FU) {
+        with_traced_level_here(c->scene.full_shading, [&](auto FU) {
             constexpr size_t lds = persistent_lds_bytes();
             auto k = path_kernel_persistent_blocks<decltype(SG)::value, decltype(WD)::value, decltype(FU)::value>;
             hipLaunchKernelGGL(k, resident_grid(c, k, lds, want, CTL_PERSIST_BPC), dim3(kBlock), lds, s, c->scene, P,
@@ -1317,3 +1352,4 @@ CTL_API ctl_status ctl_render_pass_stats(ctl_ctx* c, const ctl_pt_params* params
 }
 
 }  // extern "C"
+#endif  // CTL_PATH_KERNELS_ONLY

@@ -155,11 +155,42 @@
                 if (lazy) park.load_core(v, rng);
                 else park.load(v, sh, rng);
                 bool cont;
-                if (shadowPhase) {
+                // kShadeMedia: the medium step in front of the split into miss and hit (shading.h
+                // medium_step); `scattered`: it took the iteration, no surface is shaded
+                constexpr bool kMedia = CTL_MEDIA_OF(FULL);
+                bool scattered = false;
+                if constexpr (kMedia) {
+                    if (!shadowPhase) {
+                        park.load(v, sh, rng);
+                        const int ev = medium_step<FULL>(S, P, rng, v, h, sh);
+                        if (ev != kMediumNone) {
+                            scattered = true;
+                            v.vol_miss = h.tri == 0xffffffffu;
+                            ending = ev == kMediumEnded;
+                            shadowPhase = sh.valid;
+                            cont = sh.valid || (!ending && v.depth++ < P.max_path_length);
+                            // the loop ends with r2 still a miss: PathTracer.cu:98-111 along the new ray
+                            if (!cont && v.vol_miss) v.cl = v.cl + env_miss<FULL>(S, P, v);
+                        }
+                        // cf (a hit behind the medium) and the sampler's position go back to the park
+                        if (!scattered || cont) park.store_shaded(v, sh, rng);
+                    }
+                }
+                if (scattered) {
+                } else if (shadowPhase) {
                     if (lazy) { v.cl = park.get3(0); sh.add = park.get3(16); }
                     if (!shadow_occluded(S, shadowAny, h, sh.dist)) v.cl = v.cl + sh.add;
                     shadowPhase = false;
                     cont = !ending && v.depth++ < P.max_path_length;
+                    if constexpr (kMedia) {
+                        if (!cont && v.vol_miss) {   // as above, after the light sample's term
+                            const spec cl = v.cl;
+                            const int depth = v.depth;
+                            park.load(v, sh, rng);
+                            v.depth = depth;
+                            v.cl = cl + env_miss<FULL>(S, P, v);
+                        }
+                    }
                     if (lazy && cont) { park.store_cl(v); park.store_depth(v); }
                 } else if (h.tri == 0xffffffffu) {
                     if (lazy) park.load(v, sh, rng);
@@ -170,6 +201,7 @@
                     // sample slot (written only when the path ends), not in four VGPRs
                     // carried through every trace
                     float4* part = kList ? PS.s + ((uint32_t)*pkw & kListItemMask) : PS.s + *pkw;
+                    if constexpr (kMedia) v.vol_miss = false;
                     ending = lazy ? !shade_hit<FULL, SINGLE, Park>(S, P, rng, v, h, sh, part, &park)
                                   : !shade_hit<FULL, SINGLE>(S, P, rng, v, h, sh, part);
                     shadowPhase = sh.valid;

@@ -112,7 +112,9 @@ void prim_kernel(DevScene S_arg, PathParams P_arg, PrimParams Q, const float* s1
                     const spec f_avg = FULL ? bsdf_f<CTL_EXT_OF(FULL)>(mat, b, dg, &tex, nullptr, sf.gmat, sf.gext) : diffuse_f(mat, b);
                     spec Le = mk3s(0.0f);   // TraceResult::Le
                     if (mat.node_light_index != 0xffffffffu) Le = HitEmitter(S, sf.N, mat).Le(dg, w);
-                    const spec through = mk3s(1.0f);   // Transmittance without media
+                    // Transmittance(r, 0, prim_res.m_fDist) (PrimTracer.cu:60): 1 without a medium
+                    spec through = mk3s(1.0f);
+                    if constexpr (CTL_MEDIA_OF(FULL)) through = medium_transmittance(scene_volume(S), o, d, 0.0f, h.t);
                     if (Q.mode == CTL_PRIM_FIRST_LE || Q.mode == CTL_PRIM_FIRST_NON_DELTA_LE) {
                         L = through * Le;
                     } else if (Q.mode == CTL_PRIM_FIRST_F || Q.mode == CTL_PRIM_FIRST_NON_DELTA_F) {
@@ -122,7 +124,8 @@ void prim_kernel(DevScene S_arg, PathParams P_arg, PrimParams Q, const float* s1
                         if (S.n_lights) {
                             ShadowReq sh;
                             sh.valid = false;
-                            nee_sample<FULL>(S, rng, mat, b, dg, tex, sh, nullptr, sf.gmat, sf.gext);
+                            // UniformSampleOneLight with its default attenuated = false (PrimTracer.cu:67)
+                            nee_sample<FULL, false>(S, rng, mat, b, dg, tex, sh, nullptr, sf.gmat, sf.gext);
                             if (sh.valid) {
                                 // KernelDynamicScene::Occluded (KernelDynamicScene.cu:70-80)
                                 HitRec hs = no_hit(sh.dist - S.ray_eps);

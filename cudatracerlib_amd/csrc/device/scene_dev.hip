@@ -182,6 +182,13 @@ ctl_status validate(ctl_ctx* c, const ctl_scene_desc* d, uint32_t dirty) {
             }
         }
     }
+    if (dirty & CTL_DIRTY_VOLUMES) {
+        // one medium at most: the reference's choice among several has no defined behaviour (ctl_trace.h)
+        if (d->n_volumes > 1) { c->err = "scene_upload: more than one volume"; return CTL_ERR_INVALID; }
+        if (d->n_volumes && !d->volumes) { c->err = "scene_upload: n_volumes without the record"; return CTL_ERR_INVALID; }
+        if (d->n_volumes)
+            if (const char* why = volume_check(d->volumes[0])) { c->err = std::string("scene_upload: volume 0: ") + why; return CTL_ERR_INVALID; }
+    }
     if (dirty & CTL_DIRTY_TEXTURES) {
         for (uint32_t i = 0; i < d->n_textures; i++) {
             const ctl_texture& t = d->textures[i];
@@ -221,6 +228,12 @@ ctl_status check_clean(ctl_ctx* c, const ctl_scene_desc* d, uint32_t dirty) {
         }
     if (!(dirty & CTL_DIRTY_ENV) && (d->env_map_index != 0xffffffffu) != (c->scene.env_index != 0xffffffffu)) {
         c->err = "scene_update: the environment light changed but CTL_DIRTY_ENV is not set";
+        return CTL_ERR_INVALID;
+    }
+    if (!(dirty & CTL_DIRTY_VOLUMES) &&
+        ((d->n_volumes != 0) != (c->d_volume != nullptr) ||
+         (d->n_volumes == 1 && d->volumes && std::memcmp(d->volumes, &c->h_volume, sizeof(ctl_volume)) != 0))) {
+        c->err = "scene_update: the volume changed but CTL_DIRTY_VOLUMES is not set";
         return CTL_ERR_INVALID;
     }
     if (!(dirty & CTL_DIRTY_NODES) && (d->scene_start_node != c->scene.start_node || d->n_nodes != c->scene.n_nodes)) {
@@ -397,7 +410,18 @@ ctl_status commit_arrays(ctl_ctx* c, const ctl_scene_desc* d, uint32_t dirty, hi
     PUT(CTL_DIRTY_NODES, SA_SBVH, d->scene_bvh_nodes, d->n_scene_bvh_nodes, ctl_bvh_node, 0);
     PUT(CTL_DIRTY_NODES, SA_XF, d->node_xf, d->n_nodes, ctl_float4x4, 0);
     PUT(CTL_DIRTY_NODES, SA_IXF, d->node_inv_xf, d->n_nodes, ctl_float4x4, 0);
-    PUT(CTL_DIRTY_LIGHTS, SA_LIGHTS, d->lights, d->n_lights, ctl_light, 0);
+    // the lights array: CTL_MAX_NUM_LIGHTS slots, then the volume record (traverse.h scene_volume)
+    if (dirty & CTL_DIRTY_LIGHTS) {
+        const size_t lb = (size_t)d->n_lights * sizeof(ctl_light);   // n_lights <= CTL_MAX_NUM_LIGHTS (validate)
+        if ((r = put(c, SA_LIGHTS, d->lights, lb, kLightsArrayBytes - lb, s)) != CTL_OK) return r;
+    }
+    if (dirty & (CTL_DIRTY_LIGHTS | CTL_DIRTY_VOLUMES)) {
+        // (a lights upload cleared the tail; the uploaded record goes back with it)
+        char* at = c->sarr[SA_LIGHTS].mem.get() + kVolumeAt;
+        if (dirty & CTL_DIRTY_VOLUMES) c->h_volume = d->n_volumes ? d->volumes[0] : ctl_volume{};
+        if (dirty & CTL_DIRTY_VOLUMES) c->d_volume = d->n_volumes ? reinterpret_cast<const ctl_volume*>(at) : nullptr;
+        SD_HIP(c, hipMemcpyAsync(at, &c->h_volume, sizeof(ctl_volume), hipMemcpyHostToDevice, s));   // h_volume outlives it
+    }
     PUT(CTL_DIRTY_LIGHTS, SA_LTRIS, d->light_tris, d->n_light_tris, ctl_light_tri, 0);
     PUT(CTL_DIRTY_LIGHTS, SA_LCDF, d->light_tri_cdf, d->n_light_tri_cdf, float, 0);
     PUT(CTL_DIRTY_TEXTURES, SA_TEX, d->textures, d->n_textures, ctl_texture, 0);
@@ -526,6 +550,9 @@ ctl_status commit_arrays(ctl_ctx* c, const ctl_scene_desc* d, uint32_t dirty, hi
             if (light_is_delta(d->lights[i].kind)) c->has_delta_light = true;
     }
     S.full_shading = c->has_delta_light ? (uint32_t)kShadeLights : c->material_level;
+    // a participating medium runs the level above all others (shading.h); adding or removing the
+    // volume (CTL_DIRTY_VOLUMES) changes the level here, with no tree work
+    if (c->d_volume) S.full_shading = kShadeMedia;
     if (dirty & (CTL_DIRTY_NODES | CTL_DIRTY_MESHES | CTL_DIRTY_BVH)) {
         S.n_nodes = d->n_nodes;
         S.start_node = d->scene_start_node;
@@ -582,6 +609,8 @@ void free_scene(ctl_ctx* c) {
     c->has_delta = false;
     c->material_level = kShadeLean;
     c->has_delta_light = false;
+    c->d_volume = nullptr;
+    c->h_volume = ctl_volume{};
     c->h_wbase.clear();
     c->tree_flags = 0xffffffffu;
     c->device_eps = false;

@@ -19,9 +19,13 @@ struct PathVars {
     // rest of the path (PathTrace's bRec lives across bounces, PathTracer.cu:16,60-61)
     float dudx, dudy, dvdx, dvdy;
     bool has_partials;
+    // kShadeMedia: the last traced ray left the scene and the path went on from a medium interaction
+    // (PathTrace's r2 is then still that miss when the loop ends, PathTracer.cu:98)
+    bool vol_miss;
     __device__ __forceinline__ void begin(f2 px, f3 o, f3 d) {
         dudx = dudy = dvdx = dvdy = 0.0f;
         has_partials = false;
+        vol_miss = false;
         cl = mk3s(0.0f); cf = mk3s(1.0f);
         rori = o; rdir = d;
         last_nor = mk3s(0.0f);
@@ -73,29 +77,41 @@ __device__ __forceinline__ f2 primary_ray(const DevScene& S, SamplerDev& rng, ui
 // types do not touch.
 // lights = mat plus the point, spot and distant lights (ctl_light.h) in the light sample: a scene that holds one of
 // them runs this level, every other scene the instantiations it ran before.
-enum : int { kShadeLean = 0, kShadeFull = 1, kShadeEnv = 2, kShadeAlpha = 3, kShadeMat = 4, kShadeLights = 5 };
+// media = lights plus one homogeneous participating medium (ctl_medium.h): the medium step in front of the split
+// into miss and hit, the attenuated light sample, the escaped-path term after a medium interaction.  A scene with a
+// volume runs this level, every other scene the instantiations it ran before.
+enum : int { kShadeLean = 0, kShadeFull = 1, kShadeEnv = 2, kShadeAlpha = 3, kShadeMat = 4, kShadeLights = 5, kShadeMedia = 6 };
 // the traversal's ALPHA flag of a shading level
-#define CTL_ALPHA_OF(F) ((F) == kShadeEnv || (F) == kShadeAlpha || (F) == kShadeMat || (F) == kShadeLights)
-// levels that carry the environment light, the seven-type BSDF dispatch, and the delta lights
-#define CTL_ENV_OF(F) ((F) == kShadeEnv || (F) == kShadeMat || (F) == kShadeLights)
-#define CTL_EXT_OF(F) ((F) == kShadeMat || (F) == kShadeLights)
-#define CTL_DELTA_LIGHTS_OF(F) ((F) == kShadeLights)
+#define CTL_ALPHA_OF(F) ((F) == kShadeEnv || (F) == kShadeAlpha || (F) == kShadeMat || (F) == kShadeLights || (F) == kShadeMedia)
+// levels that carry the environment light, the seven-type BSDF dispatch, the delta lights, and the medium
+#define CTL_ENV_OF(F) ((F) == kShadeEnv || (F) == kShadeMat || (F) == kShadeLights || (F) == kShadeMedia)
+#define CTL_EXT_OF(F) ((F) == kShadeMat || (F) == kShadeLights || (F) == kShadeMedia)
+#define CTL_DELTA_LIGHTS_OF(F) ((F) == kShadeLights || (F) == kShadeMedia)
+#define CTL_MEDIA_OF(F) ((F) == kShadeMedia)
 // kernels that never trace (wavefront shade, WPT iterate) share the full instantiation
 #define CTL_NO_TRACE_LEVEL(F) ((F) == kShadeAlpha ? kShadeFull : (F))
 // Host: f(FU) with DevScene::full_shading as a constant (dispatch.h), over the
-// six levels or, for the kernels that never trace, the five they instantiate.
-// full_shading only ever holds one of the six (scene_dev.hip).
+// seven levels or, for the kernels that never trace, the six they instantiate.
+// full_shading only ever holds one of the seven (scene_dev.hip).
 template <class F>
 void with_shade_level(uint32_t full, F&& f) {
     const bool known =
-        with_level<kShadeLean, kShadeFull, kShadeEnv, kShadeAlpha, kShadeMat, kShadeLights>((int)full, f);
+        with_level<kShadeLean, kShadeFull, kShadeEnv, kShadeAlpha, kShadeMat, kShadeLights, kShadeMedia>((int)full, f);
+    assert(known);
+    (void)known;
+}
+// The path kernels of ctl_trace.hip: every level but kShadeMedia, whose path kernels are compiled in
+// path_media.hip (a code object of their own) and launched through ctl::media_launch_*.
+template <class F>
+void with_traced_level_here(uint32_t full, F&& f) {
+    const bool known = with_level<kShadeLean, kShadeFull, kShadeEnv, kShadeAlpha, kShadeMat, kShadeLights>((int)full, f);
     assert(known);
     (void)known;
 }
 template <class F>
 void with_no_trace_level(uint32_t full, F&& f) {
     const bool known =
-        with_level<kShadeLean, kShadeFull, kShadeEnv, kShadeMat, kShadeLights>((int)CTL_NO_TRACE_LEVEL(full), f);
+        with_level<kShadeLean, kShadeFull, kShadeEnv, kShadeMat, kShadeLights, kShadeMedia>((int)CTL_NO_TRACE_LEVEL(full), f);
     assert(known);
     (void)known;
 }
@@ -215,7 +231,9 @@ __device__ __forceinline__ spec env_miss(const DevScene& S, const PathParams& P,
 // shadow ray and, in sh.add, EstimateDirect(...) / pdf -- the value UniformSampleOneLight returns when the shadow
 // ray is unoccluded (it returns +0 otherwise).  gm: the material's record in the scene array (the rough-dielectric
 // calls read it there; required for FULL), R: the diffuse reflectance when already evaluated (or null).
-template <int FULL>
+// ATT: EstimateDirect's `attenuated` -- the PathTracer passes true, the PrimTracer its default false
+// (PrimTracer.cu:67) -- which only a level with a medium can tell from false.
+template <int FULL, bool ATT = CTL_MEDIA_OF(FULL)>
 __device__ __forceinline__ void nee_sample(const DevScene& S, SamplerDev& rng, const ctl_material& mat,
                                            const bsdf_rec& b, const dgeom& dg, const TexView& tex, ShadowReq& sh,
                                            const spec* R, const ctl_material* gm,
@@ -237,13 +255,84 @@ __device__ __forceinline__ void nee_sample(const DevScene& S, SamplerDev& rng, c
             if (dRec.measure != kEDiscrete)
                 weight = power_heuristic(dRec.pdf * lpdf, FULL ? bsdf_pdf<CTL_EXT_OF(FULL)>(mat, b2, gm, ge) : diffuse_pdf(mat, b2));
             spec ret = value * bsdfVal * weight;
-            ret = ret * mk3s(1.0f);
+            if constexpr (ATT) ret = ret * medium_transmittance(scene_volume(S), dRec.ref, dRec.d, 0.0f, dRec.dist);
+            else ret = ret * mk3s(1.0f);
             sh.valid = true;
             sh.d = dRec.d;
             sh.dist = dRec.dist;
             sh.add = spec_div(ret, lpdf);
         }
     }
+}
+
+// The medium in front of PathTrace's split into miss and hit (PathTracer.cu:24-58, kShadeMedia only): h is the
+// traced ray's result (t = FLT_MAX on a miss).
+//   kMediumNone       no interaction: the ray does not meet the medium, or the distance sample failed; a hit behind
+//                     the medium then carries cf * transmittance / pdfFailure and is shaded as ever, a miss ends the
+//                     path through env_miss unweighted.
+//   kMediumScattered  cf *= sigmaS * transmittance / pdfSuccess; the light sample from the medium point
+//                     (sampleAttenuatedEmitterDirect, KernelDynamicScene.cu:98-123: ONE 2-D draw shared by the emitter
+//                     choice and the light position, the transmittance to the light folded into sh.add, the power
+//                     heuristic whatever the light's measure) left in sh; the phase sample; the path goes on from the
+//                     medium point.  specular, brdf_pdf and last_nor keep their values, as in the reference.
+//   kMediumEnded      the same, and Russian roulette (:91-96) ended the path.
+// The distance is sampled over the clipped [minT, maxT], not over [0, h.t] (include/ctl_trace.h, ctl_volume).
+// Sampler draws in the reference's order: distance 1D, light 2D, phase 2D, RR 1D.
+enum : int { kMediumNone = 0, kMediumScattered = 1, kMediumEnded = 2 };
+template <int FULL>
+__device__ __forceinline__ int medium_step(const DevScene& S, const PathParams& P, SamplerDev& rng, PathVars& v,
+                                           const HitRec& h, ShadowReq& sh) {
+    sh.valid = false;
+    const ctl_volume& V = scene_volume(S);   // one record for every lane, at a kernel-uniform address
+    float minT, maxT;
+    if (!medium_intersect(V, v.rori, v.rdir, 0.0f, h.t, minT, maxT)) return kMediumNone;
+    medium_rec m;
+    if (!medium_sample_distance(V, v.rori, v.rdir, minT, maxT, rng.next1(), m)) {
+        if (h.tri != 0xffffffffu) v.cf = v.cf * spec_div(m.transmittance, m.pdfFailure);
+        return kMediumNone;
+    }
+    v.cf = v.cf * spec_div(m.sigmaS * m.transmittance, m.pdfSuccess);
+    const f3 wi = -v.rdir;
+    if (P.direct) {
+        f2 sample = rng.next2();
+        if (S.n_lights) {
+            direct_rec dRec;   // DirectSamplingRecord(mRec.p, 0); sampleEmitterDirect clears pdf
+            dRec.ref = m.p; dRec.refN = mk3s(0.0f); dRec.p = m.p; dRec.n = mk3s(0.0f);
+            dRec.d = mk3s(0.0f); dRec.dist = 0.0f; dRec.pdf = 0.0f; dRec.measure = kEArea;
+            float emPdf;
+            const uint32_t lidx = sample_emitter(S, sample, emPdf);
+            spec value = sample_light_direct<FULL>(S, lidx, dRec, sample);
+            if (dRec.pdf != 0) {
+                dRec.pdf *= emPdf;
+                value = spec_div(value, emPdf);
+            } else {
+                value = mk3s(0.0f);
+            }
+            value = value * medium_eval_transmittance(V, dRec.ref, dRec.p);
+            if (!spec_zero(value)) {
+                const float p = medium_phase_eval(V, m.p, wi, dRec.d);
+                if (p != 0) {
+                    const float weight = power_heuristic(dRec.pdf, p);
+                    sh.valid = true;
+                    sh.d = dRec.d;
+                    sh.dist = dRec.dist;
+                    sh.add = ((v.cf * value) * p) * weight;
+                }
+            }
+        }
+    }
+    f3 wo;
+    float w, pdf;
+    // a weight of 0 (the point is not in the medium after all) leaves wo unwritten in the reference;
+    // the direction stays, and cf = 0 makes every later term of the path +0
+    if (medium_phase_sample(V, m.p, wi, rng.next2(), wo, w, pdf)) v.rdir = wo;
+    v.cf = v.cf * w;
+    v.rori = m.p;
+    if (v.depth > P.rr_start_depth && !v.specular) {
+        if (rng.next1() >= spec_max(v.cf)) return kMediumEnded;
+        v.cf = spec_div(v.cf, spec_max(v.cf));
+    }
+    return kMediumScattered;
 }
 
 // One closest hit of PathTrace<DIRECT> (PathTracer.cu:35-96; DIRECT = P.direct): emission with MIS, BSDF sample,
@@ -257,7 +346,8 @@ __device__ __forceinline__ void nee_sample(const DevScene& S, SamplerDev& rng, c
 // value turns the node record and its transform into scalar loads.
 // part: when non-null (persistent kernel), the path's first-hit partials live in this memory slot instead of
 // PathVars, so they hold no VGPRs across the traces; they are read back only for a textured material, the one
-// consumer of the partials.  has_partials is then `depth > 1` (the first hit always computes them).
+// consumer of the partials.  has_partials is then `depth > 1` (the first hit always computes them); at kShadeMedia
+// the depth-1 event can be a medium interaction, so there the loop keeps v.has_partials itself.
 // pk: when non-null (persistent kernel, PK = its LDS park), the path variables other than the ray, depth / specular
 // and the sampler state are still parked in LDS on entry and are read where they are used: pX for the first-hit
 // partials, brdf_pdf and last_nor for an emitter's MIS weight, wo and brdf_pdf just before the BSDF sample, cl and
@@ -294,14 +384,19 @@ __device__ __forceinline__ bool shade_hit(const DevScene& S, const PathParams& P
             compute_partials(dg, co, dX, co, dY);
             if (part) {
                 *part = make_float4(dg.dudx, dg.dudy, dg.dvdx, dg.dvdy);
+                if constexpr (CTL_MEDIA_OF(FULL)) v.has_partials = true;
             } else {
                 v.dudx = dg.dudx; v.dudy = dg.dudy; v.dvdx = dg.dvdx; v.dvdy = dg.dvdy;
                 v.has_partials = true;
             }
         } else if (part) {
-            dg.has_partials = true;
+            // kShadeMedia: a path whose depth-1 event was a medium interaction meets its first surface here with
+            // nothing in the slot; bRec.dg then still has hasUVPartials = false and no partials (v.has_partials,
+            // a register of the persistent loop at this level only)
+            const bool written = CTL_MEDIA_OF(FULL) ? v.has_partials : true;
+            dg.has_partials = written;
             float4 q = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            if (mat.texture != 0xffffffffu) q = *part;
+            if (written && mat.texture != 0xffffffffu) q = *part;
             dg.dudx = q.x; dg.dudy = q.y; dg.dvdx = q.z; dg.dvdy = q.w;
         } else {
             dg.dudx = v.dudx; dg.dudy = v.dudy; dg.dvdx = v.dvdx; dg.dvdy = v.dvdy;

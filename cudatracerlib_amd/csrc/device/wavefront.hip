@@ -195,6 +195,7 @@ __global__ __launch_bounds__(kBlock) void wf_shade_kernel(DevScene S_arg, PathPa
             v.last_nor = mk3(wo4.w, ln2.x, ln2.y);
             v.depth = (int)(meta.z & 0xffffu);
             v.specular = (meta.z >> 16) & 1u;
+            v.vol_miss = CTL_MEDIA_OF(FULL) && ((meta.z >> 17) & 1u);
             v.has_partials = meta.w != 0u;
             if (v.has_partials) {
                 const float4 pt = W.part[i];
@@ -204,20 +205,49 @@ __global__ __launch_bounds__(kBlock) void wf_shade_kernel(DevScene S_arg, PathPa
             rng.init(s1, s2, P.nseq, P.len, meta.x, meta.y & 0xffffu, meta.y >> 16);
             HitRec h;
             h.t = hit.x; h.u = hit.y; h.v = hit.z; h.tri = (uint32_t)__float_as_int(hit.w); h.node = W.hit_node[i];
-            if (h.tri != 0xffffffffu) {
-                bool terminated = !shade_hit<FULL>(S, P, rng, v, h, sh);
+            // kShadeMedia: the medium step in front of the split into miss and hit (shading.h medium_step)
+            int ev = kMediumNone;
+            if constexpr (CTL_MEDIA_OF(FULL)) {
+                ev = medium_step<FULL>(S, P, rng, v, h, sh);
+                if (ev != kMediumNone) v.vol_miss = h.tri == 0xffffffffu;
+            }
+            if (ev != kMediumNone || h.tri != 0xffffffffu) {
+                bool terminated;
+                if (ev != kMediumNone) {
+                    terminated = ev == kMediumEnded;
+                } else {
+                    v.vol_miss = false;
+                    terminated = !shade_hit<FULL>(S, P, rng, v, h, sh);
+                }
                 pushShadow = sh.valid;
+                bool by_depth = false;
                 if (!terminated) {
                     // loop head of the next bounce: `while (depth++ < MaxPathLength)`
                     if (v.depth < P.max_path_length) { v.depth++; pushNext = true; }
-                    else terminated = true;
+                    else terminated = by_depth = true;
+                }
+                // kShadeMedia: the loop ends with r2 still the miss a medium interaction went on from
+                // (PathTracer.cu:98-111); the term follows the light sample's, so with a shadow ray
+                // pending the resolve kernel adds it (wf_resolve_media_kernel)
+                spec late = mk3s(0.0f);
+                bool has_late = false;
+                if constexpr (CTL_MEDIA_OF(FULL)) {
+                    if (terminated && v.vol_miss) {
+                        PathVars ve = v;
+                        if (by_depth) ve.depth++;   // the failed `depth++ < MaxPathLength` counted
+                        late = env_miss<FULL>(S, P, ve);
+                        has_late = true;
+                        if (!pushShadow) v.cl = v.cl + late;
+                    }
                 }
                 W.o[i] = make_float4(v.rori.x, v.rori.y, v.rori.z, v.brdf_pdf);
                 W.d[i] = make_float4(v.rdir.x, v.rdir.y, v.rdir.z, 0.0f);
                 W.cf[i] = make_float4(v.cf.x, v.cf.y, v.cf.z, v.pX.y);
                 W.wo[i] = make_float4(v.wo.x, v.wo.y, v.wo.z, v.last_nor.x);
                 W.ln[i] = make_float2(v.last_nor.y, v.last_nor.z);
-                W.meta[i] = make_uint4(meta.x, rng.d1 | (rng.d2 << 16), (uint32_t)v.depth | ((v.specular ? 1u : 0u) << 16),
+                W.meta[i] = make_uint4(meta.x, rng.d1 | (rng.d2 << 16),
+                                       (uint32_t)v.depth | ((v.specular ? 1u : 0u) << 16) |
+                                           ((CTL_MEDIA_OF(FULL) && v.vol_miss ? 1u : 0u) << 17),
                                        v.has_partials ? 1u : 0u);
                 if (v.has_partials && !meta.w) W.part[i] = make_float4(v.dudx, v.dudy, v.dvdx, v.dvdy);
                 if (terminated && !pushShadow) wf_store(P, SS, i, v.pX, mk3s(1.0f) * v.cl);
@@ -225,7 +255,9 @@ __global__ __launch_bounds__(kBlock) void wf_shade_kernel(DevScene S_arg, PathPa
                     W.sh_o[i] = make_float4(v.rori.x, v.rori.y, v.rori.z, sh.dist - S.ray_eps);
                     W.sh_d[i] = make_float4(sh.d.x, sh.d.y, sh.d.z, sh.dist);
                     // w: the path ended here -> resolve adds NEE, then AddSample
-                    W.sh_val[i] = make_float4(sh.add.x, sh.add.y, sh.add.z, terminated ? 1.0f : 0.0f);
+                    W.sh_val[i] = make_float4(sh.add.x, sh.add.y, sh.add.z, terminated ? (has_late ? 2.0f : 1.0f) : 0.0f);
+                    // the hit record is spent: it carries the late term to the resolve kernel
+                    if (has_late) W.hit[i] = make_float4(late.x, late.y, late.z, 0.0f);
                 }
             } else {
                 // miss: loop ends; environment term of PathTracer.cu:98-111
@@ -249,6 +281,22 @@ __global__ __launch_bounds__(kBlock) void wf_resolve_kernel(PathParams P, WfStat
         float4 cl4 = W.cl[i];
         spec cl = mk3(cl4.x, cl4.y, cl4.z);
         if (!W.sh_occ[i]) cl = cl + mk3(v.x, v.y, v.z);
+        W.cl[i] = make_float4(cl.x, cl.y, cl.z, cl4.w);
+        if (v.w != 0.0f) wf_store(P, SS, i, mk2(cl4.w, W.cf[i].w), mk3s(1.0f) * cl);
+    }
+}
+
+// kShadeMedia: as wf_resolve_kernel, plus the escaped-path term a path that ended after a medium
+// interaction adds after its light sample (sh_val.w = 2, the term in the spent hit record)
+__global__ __launch_bounds__(kBlock) void wf_resolve_media_kernel(PathParams P, WfState W, int bounce, SampleSlots SS) {
+    const uint32_t count = W.counts[2 * bounce + 1];
+    for (uint32_t k = blockIdx.x * kBlock + threadIdx.x; k < count; k += gridDim.x * kBlock) {
+        const uint32_t i = W.sq[k];
+        const float4 v = W.sh_val[i];
+        float4 cl4 = W.cl[i];
+        spec cl = mk3(cl4.x, cl4.y, cl4.z);
+        if (!W.sh_occ[i]) cl = cl + mk3(v.x, v.y, v.z);
+        if (v.w == 2.0f) { const float4 late = W.hit[i]; cl = cl + mk3(late.x, late.y, late.z); }
         W.cl[i] = make_float4(cl.x, cl.y, cl.z, cl4.w);
         if (v.w != 0.0f) wf_store(P, SS, i, mk2(cl4.w, W.cf[i].w), mk3s(1.0f) * cl);
     }
@@ -313,7 +361,10 @@ int wavefront_pass(ctl_ctx* c, const PathParams& P, const SampleSlots& SS, bool 
         const uint32_t* scnt = &W.counts[2 * b + 1];
         if (P.shadow_any_hit) launch_trace<1>(c, s, W.sq, scnt, &cursors[2 * b + 1], stats);
         else launch_trace<2>(c, s, W.sq, scnt, &cursors[2 * b + 1], stats);
-        hipLaunchKernelGGL(wf_resolve_kernel, dim3(persist), dim3(kBlock), 0, s, P, W, b, SS);
+        if (CTL_MEDIA_OF((int)c->scene.full_shading))
+            hipLaunchKernelGGL(wf_resolve_media_kernel, dim3(persist), dim3(kBlock), 0, s, P, W, b, SS);
+        else
+            hipLaunchKernelGGL(wf_resolve_kernel, dim3(persist), dim3(kBlock), 0, s, P, W, b, SS);
     }
     if (hipGetLastError() != hipSuccess) { c->err = "wavefront: launch failed"; return CTL_ERR_HIP; }
     return 0;

@@ -10,6 +10,7 @@
 #include "scene.h"
 #include "../ctl_env.h"
 #include "../ctl_light.h"
+#include "../ctl_medium.h"
 #include "bvh_build.h"
 #include "ref_split.h"
 #include "../ctl_shade.h"
@@ -270,6 +271,25 @@ CTL_API int32_t ctl_host_scene_add_distant_light(ctl_host_scene* s, const float 
     if (!(length(d) > 0.0f)) { set_host_error("add_distant_light: zero direction"); return -1; }
     return scene_add_delta_light(s, CTL_LIGHT_DISTANT, irradiance, distant_params(normalize(d), scene_radius),
                                  "add_distant_light");
+}
+
+CTL_API int32_t ctl_host_scene_add_homogeneous_volume(ctl_host_scene* s, const float to_world[16], const float sig_a[3],
+                                                      const float sig_s[3], const float le[3], uint32_t phase, float g) {
+    if (!s || !to_world || !sig_a || !sig_s || !le) { set_host_error("add_homogeneous_volume: null argument"); return -1; }
+    if (!s->volumes.empty()) { set_host_error("add_homogeneous_volume: a scene holds one volume at most"); return -1; }
+    ctl_volume V{};
+    V.kind = CTL_VOLUME_HOMOGENEOUS;
+    V.phase = phase;
+    V.phase_g = phase == CTL_PHASE_ISOTROPIC ? 0.0f : g;
+    for (int k = 0; k < 3; k++) { V.sig_a[k] = sig_a[k]; V.sig_s[k] = sig_s[k]; V.le[k] = le[k]; }
+    m44 m;
+    for (int k = 0; k < 16; k++) V.volume_to_world.m[k] = m.d[k] = to_world[k];
+    const m44 inv = inverse(m);   // float4x4::inverse, as for node_inv_xf
+    for (int k = 0; k < 16; k++) V.world_to_volume.m[k] = inv.d[k];
+    if (phase == CTL_PHASE_ISOTROPIC && !std::isfinite(g)) { set_host_error("add_homogeneous_volume: non-finite volume field"); return -1; }
+    if (const char* why = volume_check(V)) { set_host_error(std::string("add_homogeneous_volume: ") + why); return -1; }
+    s->volumes.push_back(V);
+    return 0;
 }
 
 CTL_API ctl_status ctl_host_scene_set_camera(ctl_host_scene* s, const float pos[3], const float target[3],
@@ -798,6 +818,16 @@ CTL_API ctl_status ctl_host_scene_compile(ctl_host_scene* s, uint32_t threads, c
     d.ray_eps = 1e-4f * length(size);   // MIN_RAYTRACE_DISTANCE_RELATIVE * |box|
     camera_setup(s->cam_pos, s->cam_tar, s->cam_up, s->cam_fov, s->cam_near, s->cam_far, s->cam_w, s->cam_h, d.camera);
     d.flags = s->flags;
+    // the medium: WorldToVolume = VolumeToWorld.inverse() (BaseVolumeRegion::Update)
+    s->kvolumes = s->volumes;
+    for (ctl_volume& V : s->kvolumes) {
+        m44 m;
+        for (int k = 0; k < 16; k++) m.d[k] = V.volume_to_world.m[k];
+        const m44 inv = inverse(m);
+        for (int k = 0; k < 16; k++) V.world_to_volume.m[k] = inv.d[k];
+    }
+    d.volumes = s->kvolumes.empty() ? nullptr : s->kvolumes.data();
+    d.n_volumes = (uint32_t)s->kvolumes.size();
     *out = d;
     s->compiled = true;
     return CTL_OK;

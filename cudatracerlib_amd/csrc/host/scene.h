@@ -53,6 +53,8 @@ struct ctl_host_scene {
     // its ctl_light_params slot, which compile() places after the area lights' triangles
     struct DeltaLight { ctl_light rec; ctl_light_params params; };
     std::vector<DeltaLight> delta_lights;
+    // the participating medium (at most one); compile() fills world_to_volume
+    std::vector<ctl_volume> volumes, kvolumes;
     bool has_camera = false;
     float cam_pos[3], cam_tar[3], cam_up[3], cam_fov, cam_near, cam_far;
     uint32_t cam_w = 0, cam_h = 0;

@@ -45,6 +45,7 @@ _ARRAYS = {
     "anim_triangles": (C.c_uint32, lambda d: 3 * d.n_anim_triangles),
     "anim_meshes": (_abi.AnimMesh, lambda d: d.n_anim_meshes),
     "materials_ext": (_abi.MaterialExt, lambda d: d.n_materials),
+    "volumes": (_abi.Volume, lambda d: d.n_volumes),
 }
 
 

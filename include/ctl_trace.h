@@ -58,7 +58,11 @@ extern "C" {
                                arithmetic's batch entries (ctl_math_eval, ctl_host_math_eval); the light
                                kinds 2-4 (CTL_LIGHT_POINT / SPOT / DISTANT, ctl_light_params in a
                                light_tris slot, record sizes unchanged), ctl_host_scene_add_point_light /
-                               _spot_light / _distant_light, ctl_light_eval, ctl_host_light_eval */
+                               _spot_light / _distant_light, ctl_light_eval, ctl_host_light_eval;
+                               one homogeneous participating medium (ctl_volume, ctl_scene_desc.volumes /
+                               n_volumes placed in front of the desc's last member materials_ext, CTL_DIRTY_VOLUMES,
+                               ctl_host_scene_add_homogeneous_volume, ctl_medium_eval,
+                               ctl_host_medium_eval) */
 
 #if defined(_WIN32)
 #define CTL_API __declspec(dllexport)
@@ -349,6 +353,46 @@ typedef struct {
 
 #define CTL_MAX_NUM_LIGHTS 16   /* KernelDynamicScene.h:26 */
 
+/* HomogeneousVolumeDensity (SceneTypes/Volumes.h:54-99) with its phase function
+ * (IsotropicPhaseFunction or HGPhaseFunction, SceneTypes/PhaseFunction.cu:9-64),
+ * flattened: the medium fills the unit cube [0,1]^3 of volume space, which
+ * volume_to_world places in the scene.
+ *   le  is carried and read by nothing: PathTrace never calls Lve.
+ * CTL_MAX_NUM_VOLUMES is the reference's array bound (Volumes.h:341) and fixes
+ * the layout; a scene holds AT MOST ONE volume and upload refuses n_volumes > 1.
+ * The reference picks among several volumes with ffsn (Volumes.cu:335-370), which
+ * returns a bit mask where an index is meant and is called with a 0-based rank:
+ * there is no defined behaviour to restate.
+ * Upload and update also refuse non-finite fields, a negative coefficient, an
+ * unknown kind or phase, and |phase_g| >= 1; the uploaded scene stays whole.
+ *
+ * Distance sampling departs from the reference in one place.  PathTrace finds
+ * [minT, maxT] by IntersectP and then hands 0 and the hit distance to
+ * sampleDistance, so the reference samples a homogeneous medium from the ray's
+ * origin wherever the ray touches the box, and a point sampled outside the box
+ * gets phase value 0 and a direction that was never written.  Here the distance
+ * is sampled over the clipped [minT, maxT], the interval tau uses; the two agree
+ * wherever the traced segment lies inside the box (camera and scene inside the
+ * fog). */
+#define CTL_MAX_NUM_VOLUMES 16
+enum { CTL_VOLUME_HOMOGENEOUS = 1 };
+enum { CTL_PHASE_ISOTROPIC = 0, CTL_PHASE_HG = 1 };
+typedef struct {
+    uint32_t kind;                  /* CTL_VOLUME_HOMOGENEOUS                   */
+    uint32_t phase;                 /* CTL_PHASE_*                              */
+    float phase_g;                  /* HGPhaseFunction::m_g (isotropic: unused) */
+    float sig_a[3];                 /* sig_a                                    */
+    float sig_s[3];                 /* sig_s                                    */
+    float le[3];                    /* le: carried, read by nothing             */
+    ctl_float4x4 volume_to_world;   /* VolumeToWorld                            */
+    ctl_float4x4 world_to_volume;   /* WorldToVolume = VolumeToWorld.inverse()  */
+} ctl_volume;                       /* 176 B */
+#if defined(__cplusplus)
+static_assert(sizeof(ctl_volume) == 176 && sizeof(ctl_volume) % 16 == 0, "ctl_volume: 176 B, a multiple of 16");
+#else
+_Static_assert(sizeof(ctl_volume) == 176 && sizeof(ctl_volume) % 16 == 0, "ctl_volume: 176 B, a multiple of 16");
+#endif
+
 /* scene flags */
 enum {
     /* decode half floats like the reference's HOST path (Math/half.h:72-84,
@@ -432,6 +476,12 @@ typedef struct {
     const ctl_anim_vertex* anim_vertices; uint32_t n_anim_vertices;
     const uint32_t* anim_triangles;     uint32_t n_anim_triangles;   /* 3 indices each */
     const ctl_anim_mesh* anim_meshes;   uint32_t n_anim_meshes;
+    /* NULL, or the scene's participating medium: at most one record (ctl_volume).
+     * The two members sit in front of materials_ext, which stays the desc's last member.
+     * Unlike the earlier additions to this struct, this one MOVES an existing member:
+     * materials_ext lies 16 bytes further on.  A caller built against an older header
+     * must be rebuilt; its materials_ext would be read as `volumes`.                    */
+    const ctl_volume* volumes;          uint32_t n_volumes;
     /* NULL, or n_materials records parallel to materials[] (BSDF types 6-8) */
     const ctl_material_ext* materials_ext;
 } ctl_scene_desc;
@@ -503,7 +553,11 @@ enum {
                                          (m_pLightStream + the ShapeSet data)        */
     CTL_DIRTY_TEXTURES = 1u << 8,     /* textures, tex_data (m_pTextureBuffer)       */
     CTL_DIRTY_ENV = 1u << 9,          /* env_map_index, env, env_data                */
-    CTL_DIRTY_ALL = (1u << 10) - 1u
+    CTL_DIRTY_VOLUMES = 1u << 10,     /* volumes (m_sVolume): the record is replaced,
+                                         added or removed without any tree work; an
+                                         update whose record differs from the uploaded
+                                         one without this flag is refused             */
+    CTL_DIRTY_ALL = (1u << 11) - 1u
 };
 
 /* UpdateKernel(DynamicScene*) (Kernel/TraceHelper.cu:182-217), called by the
@@ -1202,6 +1256,15 @@ CTL_API int32_t ctl_host_scene_add_spot_light(ctl_host_scene* s, const float pos
                                               const float intensity[3], float cutoff_deg, float beam_deg);
 CTL_API int32_t ctl_host_scene_add_distant_light(ctl_host_scene* s, const float irradiance[3], const float dir[3],
                                                  float scene_radius);
+/* HomogeneousVolumeDensity(func, to_world, sig_a, sig_s, le) with func the
+ * isotropic (phase = CTL_PHASE_ISOTROPIC, g ignored and stored as 0) or the
+ * Henyey-Greenstein (CTL_PHASE_HG, |g| < 1) phase function: the medium fills
+ * the unit cube transformed by the row-major to_world.  ctl_host_scene_compile
+ * computes world_to_volume with float4x4::inverse, as for node_inv_xf.  Returns
+ * the volume's index (0), or -1 with ctl_host_last_error: a second volume, a
+ * non-finite number, a negative coefficient, an unknown phase, |g| >= 1. */
+CTL_API int32_t ctl_host_scene_add_homogeneous_volume(ctl_host_scene* s, const float to_world[16], const float sig_a[3],
+                                                      const float sig_s[3], const float le[3], uint32_t phase, float g);
 /* PerspectiveSensor: position, target, up, fov (degrees), near/far, resolution. */
 CTL_API ctl_status ctl_host_scene_set_camera(ctl_host_scene* s, const float pos[3], const float target[3],
                                              const float up[3], float fov_deg, float near_clip,
@@ -1299,6 +1362,56 @@ CTL_API ctl_status ctl_light_eval(ctl_ctx* ctx, const ctl_light_query* d_queries
  * of ctl_light_eval bit for bit. */
 CTL_API ctl_status ctl_host_light_eval(const ctl_scene_desc* desc, const ctl_light_query* queries, int64_t n,
                                        ctl_light_result* results);
+/* The medium's arithmetic (csrc/ctl_medium.h) for an array of queries against
+ * the scene's volume.  A query carries an op and its inputs; the result carries
+ * every field the op writes, the others 0.  Without a volume, or with an op
+ * outside the five, the result is all zero with hit = 0.
+ *   INTERSECT(ori, dir, tmin, tmax)        BaseVolumeRegion::IntersectP: hit, t0, t1
+ *                                          (t0 = t1 = 0 on a miss)
+ *   TRANSMITTANCE(ori, dir, tmin, tmax)    Transmittance (TraceAlgorithms.cu:22-31)
+ *                                          over tau: transmittance; hit, t0, t1 of
+ *                                          its IntersectP
+ *   SAMPLE_DISTANCE(ori, dir, tmin, tmax, u[0])
+ *                                          HomogeneousVolumeDensity::sampleDistance:
+ *                                          hit = success, t, p, sigma_a, sigma_s (0
+ *                                          where the reference leaves them unwritten),
+ *                                          transmittance, pdf_success,
+ *                                          pdf_success_rev, pdf_failure
+ *   PHASE_EVAL(ori = p, dir = wi, wo)      KernelAggregateVolume::p: value
+ *   PHASE_SAMPLE(ori = p, dir = wi, u)     KernelAggregateVolume::Sample: wo_out,
+ *                                          value (the returned weight), pdf; hit =
+ *                                          p lies in the medium (else all 0)        */
+enum { CTL_MEDIUM_INTERSECT = 0, CTL_MEDIUM_TRANSMITTANCE = 1, CTL_MEDIUM_SAMPLE_DISTANCE = 2,
+       CTL_MEDIUM_PHASE_EVAL = 3, CTL_MEDIUM_PHASE_SAMPLE = 4 };
+typedef struct {
+    uint32_t op;
+    float ori[3];          /* ray origin, or the point p                              */
+    float dir[3];          /* ray direction, or wi                                    */
+    float wo[3];           /* PHASE_EVAL: wo                                          */
+    float tmin, tmax;
+    float u[2];            /* SAMPLE_DISTANCE: u[0]; PHASE_SAMPLE: both               */
+} ctl_medium_query;        /* 56 B */
+typedef struct {
+    uint32_t hit;
+    float t0, t1;
+    float t;
+    float p[3];
+    float transmittance[3];
+    float sigma_a[3];
+    float sigma_s[3];
+    float pdf_success, pdf_success_rev, pdf_failure;
+    float value;
+    float pdf;
+    float wo_out[3];
+} ctl_medium_result;       /* 96 B */
+/* On the device, for the uploaded scene: d_queries and d_results are device
+ * arrays of n records. */
+CTL_API ctl_status ctl_medium_eval(ctl_ctx* ctx, const ctl_medium_query* d_queries, int64_t n,
+                                   ctl_medium_result* d_results, void* stream);
+/* The same for a scene description, on the CPU (no GPU needed): the arithmetic
+ * of ctl_medium_eval bit for bit. */
+CTL_API ctl_status ctl_host_medium_eval(const ctl_scene_desc* desc, const ctl_medium_query* queries, int64_t n,
+                                        ctl_medium_result* results);
 /* The scalar arithmetic under every kernel, for arrays of inputs: function fn
  * of a[i] (and b[i] for the two-argument functions; b is ignored otherwise) to
  * out[i], a 32-bit word holding the float's bits or the integer result.  The
