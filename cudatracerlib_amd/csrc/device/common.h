@@ -628,4 +628,11 @@ int intersect_launch(ctl_ctx* c, int64_t n, const ctl_ray* rays, ctl_hit* hits, 
                      int64_t n2 = 0, const ctl_ray* rays2 = nullptr, ctl_hit* hits2 = nullptr,
                      const uint32_t* dcount = nullptr, uint32_t band_w = 0);
 int count_rays(ctl_ctx* c, uint64_t n, hipStream_t s);
+// path_media.hip: launch_path / launch_path_blocks (path_kernels.h) of the level kShadeMedia;
+// false, and nothing launched, when the uploaded scene has another level
+bool media_launch_path(ctl_ctx* c, bool persistent, bool stats, const PathParams& P, const float* s1, const float2* s2,
+                       uint64_t threads, uint64_t want, dim3 grid, unsigned long long* cursor, ctl_pixel* fb, SampleSlots PS,
+                       uint32_t tbl, hipStream_t s);
+bool media_launch_blocks(ctl_ctx* c, const PathParams& P, const float* s1, const float2* s2, uint64_t items, uint64_t want,
+                         unsigned long long* cursor, SampleSlots PS, const uint32_t* own_tbl, hipStream_t s);
 }

@@ -1,5 +1,5 @@
 // The loop of the persistent path kernels, included as the body of both kernel
-// templates in ctl_trace.hip (path_kernel_persistent, path_kernel_persistent_blocks)
+// templates in path_kernels.h (path_kernel_persistent, path_kernel_persistent_blocks)
 // so that each compiles exactly as if it were written out.  The including kernel
 // provides: template parameters STATS, SINGLE, WIDE, FULL; the type OWN (ownership
 // policy, common.h); its arguments S_arg, P_arg, s1, s2, items, cursor, counters,

@@ -524,35 +524,26 @@ ctl_status commit_arrays(ctl_ctx* c, const ctl_scene_desc* d, uint32_t dirty, hi
     }
     set_constants(c, d, dirty);
     if (dirty & (CTL_DIRTY_MATERIALS | CTL_DIRTY_ENV)) {
-        S.full_shading = kShadeLean;
-        S.alpha = 0;
-        for (uint32_t i = 0; i < d->n_materials; i++) {
-            const ctl_material& m = d->materials[i];
-            if (m.bsdf_type != CTL_BSDF_DIFFUSE || m.texture != 0xffffffffu || m.alpha_state) S.full_shading = kShadeFull;
-            if (m.alpha_state) S.alpha = 1;   // DynamicScene.cpp:586 doAlphaMapping
-        }
-        if (S.alpha) S.full_shading = kShadeAlpha;
-        if (S.env_index != 0xffffffffu) S.full_shading = kShadeEnv;
-        // the five further BSDF types run their own level (shading.h), so every
-        // other scene keeps the kernels it had
+        bool shaded = false, alpha = false, ext = false;
         c->has_delta = false;
         for (uint32_t i = 0; i < d->n_materials; i++) {
-            if (bsdf_ext_type(d->materials[i].bsdf_type)) S.full_shading = kShadeMat;
-            if (d->materials[i].combined_type & kEDelta) c->has_delta = true;
+            const ctl_material& m = d->materials[i];
+            if (m.bsdf_type != CTL_BSDF_DIFFUSE || m.texture != 0xffffffffu || m.alpha_state) shaded = true;
+            if (m.alpha_state) alpha = true;   // DynamicScene.cpp:586 doAlphaMapping
+            if (bsdf_ext_type(m.bsdf_type)) ext = true;
+            if (m.combined_type & kEDelta) c->has_delta = true;
         }
-        c->material_level = S.full_shading;
+        S.alpha = alpha ? 1 : 0;
+        c->material_level = (uint32_t)material_level(shaded, alpha, S.env_index != 0xffffffffu, ext);
     }
-    // a point, spot or distant light runs the level of its own (shading.h); every
-    // other scene keeps the level its materials and environment ask for
     if (dirty & CTL_DIRTY_LIGHTS) {
         c->has_delta_light = false;
         for (uint32_t i = 0; i < d->n_lights; i++)
             if (light_is_delta(d->lights[i].kind)) c->has_delta_light = true;
     }
-    S.full_shading = c->has_delta_light ? (uint32_t)kShadeLights : c->material_level;
-    // a participating medium runs the level above all others (shading.h); adding or removing the
-    // volume (CTL_DIRTY_VOLUMES) changes the level here, with no tree work
-    if (c->d_volume) S.full_shading = kShadeMedia;
+    // the scene's level (dispatch.h scene_level); adding or removing the volume (CTL_DIRTY_VOLUMES)
+    // changes it here, with no tree work
+    S.full_shading = (uint32_t)scene_level((int)c->material_level, c->has_delta_light, c->d_volume != nullptr);
     if (dirty & (CTL_DIRTY_NODES | CTL_DIRTY_MESHES | CTL_DIRTY_BVH)) {
         S.n_nodes = d->n_nodes;
         S.start_node = d->scene_start_node;

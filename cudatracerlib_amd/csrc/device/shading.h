@@ -80,19 +80,20 @@ __device__ __forceinline__ f2 primary_ray(const DevScene& S, SamplerDev& rng, ui
 // media = lights plus one homogeneous participating medium (ctl_medium.h): the medium step in front of the split
 // into miss and hit, the attenuated light sample, the escaped-path term after a medium interaction.  A scene with a
 // volume runs this level, every other scene the instantiations it ran before.
-enum : int { kShadeLean = 0, kShadeFull = 1, kShadeEnv = 2, kShadeAlpha = 3, kShadeMat = 4, kShadeLights = 5, kShadeMedia = 6 };
-// the traversal's ALPHA flag of a shading level
-#define CTL_ALPHA_OF(F) ((F) == kShadeEnv || (F) == kShadeAlpha || (F) == kShadeMat || (F) == kShadeLights || (F) == kShadeMedia)
-// levels that carry the environment light, the seven-type BSDF dispatch, the delta lights, and the medium
-#define CTL_ENV_OF(F) ((F) == kShadeEnv || (F) == kShadeMat || (F) == kShadeLights || (F) == kShadeMedia)
-#define CTL_EXT_OF(F) ((F) == kShadeMat || (F) == kShadeLights || (F) == kShadeMedia)
-#define CTL_DELTA_LIGHTS_OF(F) ((F) == kShadeLights || (F) == kShadeMedia)
-#define CTL_MEDIA_OF(F) ((F) == kShadeMedia)
-// kernels that never trace (wavefront shade, WPT iterate) share the full instantiation
-#define CTL_NO_TRACE_LEVEL(F) ((F) == kShadeAlpha ? kShadeFull : (F))
-// Host: f(FU) with DevScene::full_shading as a constant (dispatch.h), over the
-// seven levels or, for the kernels that never trace, the six they instantiate.
-// full_shading only ever holds one of the seven (scene_dev.hip).
+// The levels, what each carries and which one a scene runs are dispatch.h's table and scene_level; the
+// names below read that table: the traversal's ALPHA flag of a level, the levels that carry the environment
+// light, the seven-type BSDF dispatch, the delta lights and the medium, and the instantiation the kernels
+// that never trace (wavefront shade, WPT iterate) run for a level.
+#define CTL_ALPHA_OF(F) (ctl::level_alpha(F))
+#define CTL_ENV_OF(F) (ctl::level_env(F))
+#define CTL_EXT_OF(F) (ctl::level_ext(F))
+#define CTL_DELTA_LIGHTS_OF(F) (ctl::level_delta_lights(F))
+#define CTL_MEDIA_OF(F) (ctl::level_media(F))
+#define CTL_NO_TRACE_LEVEL(F) (ctl::level_no_trace(F))
+// Host: f(FU) with DevScene::full_shading as a constant (dispatch.h), over the seven levels or, for the
+// kernels that never trace, the six they instantiate.  full_shading only ever holds one of the seven
+// (scene_dev.hip).  The PathTracer's kernels have their lists at their launch (path_kernels.h): the levels
+// of ctl_trace.hip's code object and of path_media.hip's.
 template <class F>
 void with_shade_level(uint32_t full, F&& f) {
     const bool known =
@@ -100,18 +101,10 @@ void with_shade_level(uint32_t full, F&& f) {
     assert(known);
     (void)known;
 }
-// The path kernels of ctl_trace.hip: every level but kShadeMedia, whose path kernels are compiled in
-// path_media.hip (a code object of their own) and launched through ctl::media_launch_*.
-template <class F>
-void with_traced_level_here(uint32_t full, F&& f) {
-    const bool known = with_level<kShadeLean, kShadeFull, kShadeEnv, kShadeAlpha, kShadeMat, kShadeLights>((int)full, f);
-    assert(known);
-    (void)known;
-}
 template <class F>
 void with_no_trace_level(uint32_t full, F&& f) {
     const bool known =
-        with_level<kShadeLean, kShadeFull, kShadeEnv, kShadeMat, kShadeLights, kShadeMedia>((int)CTL_NO_TRACE_LEVEL(full), f);
+        with_level<kShadeLean, kShadeFull, kShadeEnv, kShadeMat, kShadeLights, kShadeMedia>(CTL_NO_TRACE_LEVEL((int)full), f);
     assert(known);
     (void)known;
 }

@@ -1,7 +1,8 @@
 """Every file libctl_trace.so is compiled from is in the source fingerprint
 (buildid.py): the persistent path kernels' loop lives in a file of its own,
-included as the body of two kernel templates, and a profile of that kernel must
-not be matched to a binary built from an edited loop."""
+included as the body of two kernel templates, and those templates in a header
+that two code objects include; a profile of that kernel must not be matched to
+a binary built from an edited loop or header."""
 import os
 import shutil
 import sys
@@ -27,6 +28,7 @@ def test_every_csrc_file_changes_the_fingerprint(tmp_path):
     assert source_fingerprint(dst) == base
     rel = [os.path.relpath(os.path.join(d, n), dst) for d, _, names in os.walk(os.path.join(dst, CSRC)) for n in names]
     assert os.path.join(CSRC, "device", "persistent_loop.h") in rel
+    assert os.path.join(CSRC, "device", "path_kernels.h") in rel
     for r in sorted(rel):
         path = os.path.join(dst, r)
         with open(path, "rb") as f:

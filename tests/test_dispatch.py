@@ -11,10 +11,23 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEVICE = os.path.join(ROOT, "cudatracerlib_amd", "csrc", "device")
 
-# the shading levels of common.h: lean, full, env, alpha, mat
-ALL_LEVELS = (0, 1, 2, 3, 4)
-NO_TRACE_LEVELS = (0, 1, 2, 4)   # kernels that never trace have no alpha instantiation
-PROBED = range(-1, 7)
+# the shading levels of dispatch.h: lean, full, env, alpha, mat, lights, media
+ALL_LEVELS = (0, 1, 2, 3, 4, 5, 6)
+TRACE_LEVELS = (0, 1, 2, 3, 4, 5)         # the path kernels of ctl_trace.hip's code object
+MEDIA_LEVELS = (6,)                       # ... and of path_media.hip's
+NO_TRACE_LEVELS = (0, 1, 2, 4, 5, 6)      # kernels that never trace have no alpha instantiation
+PROBED = range(-1, 9)
+
+# level: (ALPHA, ENV, EXT, DELTA_LIGHTS, MEDIA, no-trace level)
+TABLE = {
+    0: (0, 0, 0, 0, 0, 0),
+    1: (0, 0, 0, 0, 0, 1),
+    2: (1, 1, 0, 0, 0, 2),
+    3: (1, 0, 0, 0, 0, 1),
+    4: (1, 1, 1, 0, 0, 4),
+    5: (1, 1, 1, 1, 0, 5),
+    6: (1, 1, 1, 1, 1, 6),
+}
 
 SRC = r"""
 #include "dispatch.h"
@@ -23,7 +36,7 @@ SRC = r"""
 
 template <int... L>
 void levels(const char* tag) {
-    for (int full = -1; full < 7; full++) {
+    for (int full = -1; full < 9; full++) {
         const bool hit = ctl::with_level<L...>(
             full, [&](auto FU) { std::printf("%s %d call %d\n", tag, full, (int)decltype(FU)::value); });
         std::printf("%s %d hit %d\n", tag, full, (int)hit);
@@ -44,8 +57,19 @@ int main() {
             std::printf("tree2 %d %d call %d %d\n", single, wide, (int)decltype(SG)::value, (int)decltype(WD)::value);
         });
     }
-    levels<0, 1, 2, 3, 4>("all");
-    levels<0, 1, 2, 4>("notrace");
+    levels<0, 1, 2, 3, 4, 5, 6>("all");
+    levels<0, 1, 2, 3, 4, 5>("trace");
+    levels<6>("media");
+    levels<0, 1, 2, 4, 5, 6>("notrace");
+    for (int l = 0; l < ctl::kShadeLevelCount; l++)
+        std::printf("row %d %d %d %d %d %d %d\n", l, (int)ctl::level_alpha(l), (int)ctl::level_env(l),
+                    (int)ctl::level_ext(l), (int)ctl::level_delta_lights(l), (int)ctl::level_media(l),
+                    ctl::level_no_trace(l));
+    for (int i = 0; i < 64; i++) {
+        const bool shaded = i & 1, alpha = i & 2, env = i & 4, ext = i & 8, delta = i & 16, volume = i & 32;
+        std::printf("scene %d %d %d %d %d %d %d\n", shaded, alpha, env, ext, delta, volume,
+                    ctl::scene_level(shaded, alpha, env, ext, delta, volume));
+    }
     return 0;
 }
 """
@@ -90,7 +114,8 @@ def test_tree_without_stats(lines):
     assert len({ln[4:] for ln in calls}) == 4
 
 
-@pytest.mark.parametrize("tag,listed", [("all", ALL_LEVELS), ("notrace", NO_TRACE_LEVELS)])
+@pytest.mark.parametrize("tag,listed", [("all", ALL_LEVELS), ("notrace", NO_TRACE_LEVELS), ("trace", TRACE_LEVELS),
+                                        ("media", MEDIA_LEVELS)])
 def test_levels(lines, tag, listed):
     for full in PROBED:
         calls = [ln[3] for ln in lines if ln[:3] == (tag, full, "call")]
@@ -99,3 +124,23 @@ def test_levels(lines, tag, listed):
             assert calls == [full] and hit == [1]             # once, with that constant
         else:
             assert calls == [] and hit == [0]                 # nothing called, and reported
+
+
+def test_level_table(lines):
+    rows = {ln[1]: ln[2:] for ln in lines if ln[0] == "row"}
+    assert rows == TABLE                                      # every level, and no other
+    # the two level lists are what the table says: a no-trace level maps to itself, and
+    # ctl_trace.hip's and path_media.hip's lists split the levels by MEDIA
+    assert tuple(sorted({row[5] for row in TABLE.values()})) == NO_TRACE_LEVELS
+    assert all(TABLE[nt][5] == nt for nt in NO_TRACE_LEVELS)
+    assert tuple(l for l in ALL_LEVELS if TABLE[l][4]) == MEDIA_LEVELS
+    assert tuple(l for l in ALL_LEVELS if not TABLE[l][4]) == TRACE_LEVELS
+
+
+def test_scene_level(lines):
+    got = {ln[1:7]: ln[7] for ln in lines if ln[0] == "scene"}
+    assert len(got) == 64
+    # media > lights > mat > env > alpha > full > lean
+    for (shaded, alpha, env, ext, delta, volume), level in got.items():
+        want = 6 if volume else 5 if delta else 4 if ext else 2 if env else 3 if alpha else 1 if shaded else 0
+        assert level == want, (shaded, alpha, env, ext, delta, volume)
