@@ -44,7 +44,8 @@ __all__ = ["HostScene", "Tracer", "PathTracer", "BlockSampler", "BLOCK_INFO_DTYP
            "thindielectric_material", "conductor_material", "roughconductor_material", "plastic_material",
            "fresnel_diffuse_reflectance", "host_bsdf_eval", "host_math_eval", "MATH_FUNCTIONS",
            "LIGHT_QUERY_DTYPE", "LIGHT_RESULT_DTYPE", "host_light_eval",
-           "MEDIUM_QUERY_DTYPE", "MEDIUM_RESULT_DTYPE", "host_medium_eval"]
+           "MEDIUM_QUERY_DTYPE", "MEDIUM_RESULT_DTYPE", "host_medium_eval",
+           "SENSOR_QUERY_DTYPE", "SENSOR_RESULT_DTYPE", "SENSOR_KINDS", "host_sensor_eval"]
 
 
 def lib():
@@ -289,6 +290,26 @@ def host_medium_eval(desc, queries):
     out = np.zeros(q.shape[0], dtype=MEDIUM_RESULT_DTYPE)
     _check(lib().ctl_host_medium_eval(C.byref(desc), q.ctypes.data, q.shape[0], out.ctypes.data), None,
            "ctl_host_medium_eval")
+    return out
+
+
+SENSOR_QUERY_DTYPE = np.dtype([("pixel_sample", "<f4", 2), ("aperture_sample", "<f4", 2), ("differential", "<u4")])
+SENSOR_RESULT_DTYPE = np.dtype([("o", "<f4", 3), ("d", "<f4", 3), ("ox", "<f4", 3), ("dx", "<f4", 3), ("oy", "<f4", 3),
+                                ("dy", "<f4", 3), ("has_differentials", "<u4"), ("pad", "<u4")])
+# HostScene.set_sensor kinds -> the reference's sensor type ids (_abi.CTL_SENSOR_*)
+SENSOR_KINDS = {"spherical": _abi.CTL_SENSOR_SPHERICAL, "perspective": _abi.CTL_SENSOR_PERSPECTIVE,
+                "thinlens": _abi.CTL_SENSOR_THINLENS, "orthographic": _abi.CTL_SENSOR_ORTHOGRAPHIC,
+                "telecentric": _abi.CTL_SENSOR_TELECENTRIC}
+
+
+def host_sensor_eval(desc, queries):
+    """Sensor::sampleRay (differential = 0) or Sensor::sampleRayDifferential of desc's sensor for an array of
+    SENSOR_QUERY_DTYPE queries, on the CPU (ctl_host_sensor_eval): SENSOR_RESULT_DTYPE results, the device
+    entry's arithmetic bit for bit."""
+    q = np.ascontiguousarray(queries, dtype=SENSOR_QUERY_DTYPE)
+    out = np.zeros(q.shape[0], dtype=SENSOR_RESULT_DTYPE)
+    _check(lib().ctl_host_sensor_eval(C.byref(desc), q.ctypes.data, q.shape[0], out.ctypes.data), None,
+           "ctl_host_sensor_eval")
     return out
 
 
@@ -600,6 +621,24 @@ class HostScene:
         f3 = C.c_float * 3
         _check(self._L.ctl_host_scene_set_camera(self._h, f3(*pos), f3(*target), f3(*up), fov_deg, near, far,
                                                   width, height), None, "set_camera")
+
+    def set_sensor(self, kind, aperture_radius=0.0, focus_distance=None, screen_scale=(1, 1)):
+        """Which of the reference's five sensors the scene is seen through: kind is "perspective", "thinlens",
+        "orthographic", "telecentric" or "spherical" (SENSOR_KINDS); called after set_camera, whose position, fov,
+        near / far and resolution it keeps.  focus_distance is needed by "thinlens" and "telecentric".  On a compiled
+        scene the description (self.desc) takes the new camera and sensor records at once: hand it to
+        Tracer.update_scene(desc, 0), no recompile."""
+        if kind not in SENSOR_KINDS:
+            raise ValueError(f"set_sensor: kind must be one of {sorted(SENSOR_KINDS)}")
+        focus = 0.0 if focus_distance is None else float(focus_distance)
+        _check(self._L.ctl_host_scene_set_sensor(self._h, SENSOR_KINDS[kind], float(aperture_radius), focus,
+                                                  (C.c_float * 2)(*[float(x) for x in screen_scale])), None, "set_sensor")
+        if getattr(self, "desc", None) is not None:
+            self._sensor = _abi.Sensor()   # owned here: the description points at it
+            _check(self._L.ctl_host_scene_sensor_state(self._h, C.byref(self.desc.camera), C.byref(self._sensor)), None,
+                   "sensor_state")
+            self.desc.sensor = C.pointer(self._sensor)
+        return self
 
     def set_flags(self, flags):
         _check(self._L.ctl_host_scene_set_flags(self._h, flags), None, "set_flags")
@@ -923,6 +962,12 @@ class Tracer:
         memory (ctl_light_eval); results to n ctl_light_result records in device memory."""
         _check(self._L.ctl_light_eval(self._ctx, int(queries_ptr), int(n), int(results_ptr), stream or None), self._ctx,
                "ctl_light_eval")
+
+    def sensor_eval(self, n, queries_ptr, results_ptr, stream=0):
+        """Sensor::sampleRay / sampleRayDifferential of the uploaded scene's sensor for n ctl_sensor_query records
+        in device memory (ctl_sensor_eval); results to n ctl_sensor_result records in device memory."""
+        _check(self._L.ctl_sensor_eval(self._ctx, int(queries_ptr), int(n), int(results_ptr), stream or None), self._ctx,
+               "ctl_sensor_eval")
 
     def medium_eval(self, n, queries_ptr, results_ptr, stream=0):
         """The medium's five operations of the uploaded scene's volume for n ctl_medium_query records in

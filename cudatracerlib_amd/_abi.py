@@ -205,6 +205,23 @@ class MediumResult(C.Structure):     # ctl_medium_result, 96 B
                 ("value", C.c_float), ("pdf", C.c_float), ("wo_out", C.c_float * 3)]
 
 
+CTL_SENSOR_SPHERICAL, CTL_SENSOR_PERSPECTIVE, CTL_SENSOR_THINLENS, CTL_SENSOR_ORTHOGRAPHIC, CTL_SENSOR_TELECENTRIC = 1, 2, 3, 4, 5
+
+
+class Sensor(C.Structure):           # ctl_sensor (which of the reference's five sensors ctl_camera describes), 32 B
+    _fields_ = [("type", C.c_uint32), ("aperture_radius", C.c_float), ("focus_distance", C.c_float),
+                ("screen_scale", C.c_float * 2), ("pad", C.c_uint32 * 3)]
+
+
+class SensorQuery(C.Structure):      # ctl_sensor_query, 20 B
+    _fields_ = [("pixel_sample", C.c_float * 2), ("aperture_sample", C.c_float * 2), ("differential", C.c_uint32)]
+
+
+class SensorResult(C.Structure):     # ctl_sensor_result, 80 B
+    _fields_ = [("o", C.c_float * 3), ("d", C.c_float * 3), ("ox", C.c_float * 3), ("dx", C.c_float * 3),
+                ("oy", C.c_float * 3), ("dy", C.c_float * 3), ("has_differentials", C.c_uint32), ("pad", C.c_uint32)]
+
+
 class SceneDesc(C.Structure):
     _fields_ = [
         ("tri_data", C.POINTER(TriangleData)), ("n_tri_data", C.c_uint64),
@@ -235,6 +252,7 @@ class SceneDesc(C.Structure):
         ("anim_triangles", C.POINTER(C.c_uint32)), ("n_anim_triangles", C.c_uint32),
         ("anim_meshes", C.POINTER(AnimMesh)), ("n_anim_meshes", C.c_uint32),
         ("volumes", C.POINTER(Volume)), ("n_volumes", C.c_uint32),
+        ("sensor", C.POINTER(Sensor)),
         ("materials_ext", C.POINTER(MaterialExt)),
     ]
 
@@ -358,6 +376,10 @@ SYMBOLS = [
     ("ctl_host_medium_eval", C.c_int32, [C.POINTER(SceneDesc), _vp, C.c_int64, _vp]),
     ("ctl_medium_eval", C.c_int32, [_vp, _vp, C.c_int64, _vp, _vp]),
     ("ctl_light_eval", C.c_int32, [_vp, _vp, C.c_int64, _vp, _vp]),
+    ("ctl_host_scene_set_sensor", C.c_int32, [_vp, C.c_uint32, C.c_float, C.c_float, _vp]),
+    ("ctl_host_scene_sensor_state", C.c_int32, [_vp, C.POINTER(Camera), C.POINTER(Sensor)]),
+    ("ctl_sensor_eval", C.c_int32, [_vp, _vp, C.c_int64, _vp, _vp]),
+    ("ctl_host_sensor_eval", C.c_int32, [C.POINTER(SceneDesc), _vp, C.c_int64, _vp]),
     ("ctl_host_scene_set_camera", C.c_int32, [_vp, _vp, _vp, _vp, C.c_float, C.c_float, C.c_float,
                                               C.c_uint32, C.c_uint32]),
     ("ctl_host_scene_set_flags", C.c_int32, [_vp, C.c_uint32]),

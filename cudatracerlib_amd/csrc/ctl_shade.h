@@ -164,15 +164,21 @@ CTL_HD spec refl(const ctl_material& m) { return mk3(m.reflectance[0], m.reflect
 
 // diffuse::sample up to its return value (BSDF_Simple.cu:7-24, pure
 // EDiffuseReflection): false = the reference returns 0.
-// Warp::squareToCosineHemisphere + squareToUniformDiskConcentric (Math/Warp.h:61-125)
-CTL_HD f3 square_to_cosine_hemisphere(f2 sample) {
+// Warp::squareToUniformDiskConcentric (Math/Warp.h:102-125): the cosine hemisphere's disk and the
+// lens of the thin-lens and telecentric sensors (ctl_sensor.h)
+CTL_HD f2 square_to_uniform_disk_concentric(f2 sample) {
     float r1 = 2.0f * sample.x - 1.0f, r2 = 2.0f * sample.y - 1.0f;
     float phi, r;
     if (r1 == 0 && r2 == 0) { r = phi = 0; }
     else if (r1 * r1 > r2 * r2) { r = r1; phi = (CTL_PI / 4.0f) * (r2 / r1); }
     else { r = r2; phi = (CTL_PI / 2.0f) - (r1 / r2) * (CTL_PI / 4.0f); }
     float sinPhi = cr_sin(phi), cosPhi = cr_cos(phi);
-    f2 p = mk2(r * cosPhi, r * sinPhi);
+    return mk2(r * cosPhi, r * sinPhi);
+}
+
+// Warp::squareToCosineHemisphere (Math/Warp.h:61-68)
+CTL_HD f3 square_to_cosine_hemisphere(f2 sample) {
+    f2 p = square_to_uniform_disk_concentric(sample);
     float z = sqrtf(1.0f - p.x * p.x - p.y * p.y);
     return mk3(p.x, p.y, z);
 }

@@ -15,6 +15,7 @@
 #include "../ctl_env.h"
 #include "../ctl_light.h"
 #include "../ctl_medium.h"
+#include "../ctl_sensor.h"
 
 namespace ctl {
 
@@ -64,6 +65,15 @@ struct SamplerDev {   // SequenceSampler (Kernel/Sampler_device.h:59-113)
         x += p.x; y += p.y;
         x += q.x; y += q.y;
         d2 = d2 + 1 == len ? 0u : d2 + 1;
+        return mk2(fracf_ref(x), fracf_ref(y));
+    }
+    // the value next2() returned as the sequence's 2-D draw number `draw`, whatever the counters are now
+    __device__ __forceinline__ f2 peek2(uint32_t draw) const {
+        const uint32_t k = draw % len;
+        float2 p = s2[k * nseq + a], q = s2[k * nseq + b];
+        float x = 0.0f, y = 0.0f;
+        x += p.x; y += p.y;
+        x += q.x; y += q.y;
         return mk2(fracf_ref(x), fracf_ref(y));
     }
 };
@@ -452,11 +462,14 @@ struct MeshRegion {
 // KernelDynamicScene stream, reused by ctl_scene_update while it fits.
 // SA_LIGHTS is allocated whole at its first upload and never grows: CTL_MAX_NUM_LIGHTS ctl_light slots,
 // then the scene's ctl_volume at byte kVolumeAt (traverse.h scene_volume reads it there, ctl_ctx::d_volume
-// points at it).  Its `bytes` counts the uploaded lights only.  Whoever re-puts or resizes SA_LIGHTS keeps
-// the tail: scene_dev.hip commit_arrays writes the record back after every lights upload.
+// points at it), then the scene's ctl_sensor at byte kSensorAt (traverse.h scene_sensor).  Its `bytes` counts
+// the uploaded lights only.  Whoever re-puts or resizes SA_LIGHTS keeps the tail: scene_dev.hip commit_arrays
+// writes the volume record back after every lights upload, and the sensor record on every commit.
 constexpr size_t kVolumeAt = CTL_MAX_NUM_LIGHTS * sizeof(ctl_light);
-constexpr size_t kLightsArrayBytes = kVolumeAt + sizeof(ctl_volume);
+constexpr size_t kSensorAt = kVolumeAt + sizeof(ctl_volume);
+constexpr size_t kLightsArrayBytes = kSensorAt + sizeof(ctl_sensor);
 static_assert(kVolumeAt % 16 == 0, "the volume record is read at a 16-byte aligned address behind the light slots");
+static_assert(kSensorAt % 16 == 0, "the sensor record is read at a 16-byte aligned address behind the volume record");
 enum SceneArr : int {
     SA_BVH, SA_WOOP, SA_IDX, SA_TRI, SA_MATS, SA_MESHES, SA_NODES, SA_SBVH, SA_XF, SA_IXF, SA_LIGHTS, SA_LTRIS,
     SA_LCDF, SA_LUT, SA_TEX, SA_TEXDATA, SA_ENV, SA_ENVDATA, SA_WBVH, SA_SWBVH, SA_WBASE, SA_MATX,
@@ -488,6 +501,7 @@ struct ctl_ctx {
     bool has_delta_light = false;               // some uploaded light is a point, spot or distant light
     ctl_volume h_volume{};                      // host copy of that record (all zero without one)
     const ctl_volume* d_volume = nullptr;       // the uploaded scene's medium (behind the light slots of SA_LIGHTS), null without one
+    ctl_sensor h_sensor = ctl::sensor_default(); // host copy of the uploaded sensor record (the perspective one without a record)
     uint32_t nseq = 4096, len = 30;
     ctl::DevPool fixed;                         // owns the arrays allocated once by ctl_create
     float* d_s1[2] = {nullptr, nullptr};        // (fixed)
@@ -635,4 +649,13 @@ bool media_launch_path(ctl_ctx* c, bool persistent, bool stats, const PathParams
                        uint32_t tbl, hipStream_t s);
 bool media_launch_blocks(ctl_ctx* c, const PathParams& P, const float* s1, const float2* s2, uint64_t items, uint64_t want,
                          unsigned long long* cursor, SampleSlots PS, const uint32_t* own_tbl, hipStream_t s);
+// path_sensors.hip: the same for the level kShadeSensors, and the camera-ray batch of ctl_camera_rays at that level
+bool sensors_launch_path(ctl_ctx* c, bool persistent, bool stats, const PathParams& P, const float* s1, const float2* s2,
+                         uint64_t threads, uint64_t want, dim3 grid, unsigned long long* cursor, ctl_pixel* fb,
+                         SampleSlots PS, uint32_t tbl, hipStream_t s);
+bool sensors_launch_blocks(ctl_ctx* c, const PathParams& P, const float* s1, const float2* s2, uint64_t items,
+                           uint64_t want, unsigned long long* cursor, SampleSlots PS, const uint32_t* own_tbl,
+                           hipStream_t s);
+bool sensors_launch_camera_rays(ctl_ctx* c, const PathParams& P, const float* s1, const float2* s2, uint64_t items,
+                                ctl_ray* rays, hipStream_t s);
 }

@@ -15,7 +15,7 @@
 //                      OwnList ownership policy, common.h)
 //   sampler_kernel     SequenceSamplerData tables of a pass (Sampler.cu, CudaRandom.cu)
 // The path kernel templates (path_kernel, path_kernel_persistent, path_kernel_persistent_blocks) and
-// their launch are path_kernels.h, instantiated here for every shading level but kShadeMedia
+// their launch are path_kernels.h, instantiated here for every shading level but kShadeMedia and kShadeSensors
 // (path_media.hip).  The wavefront schedule lives in wavefront.hip.
 #include <hip/hip_runtime.h>
 
@@ -54,7 +54,8 @@ static_assert(sizeof(ctl_texture) == 380, "ctl_texture is 380 B");
 static_assert(sizeof(ctl_pixel_variance) == 44, "PixelVarianceInfo is 44 B");
 
 #include "path_kernels.h"
-// the levels whose path kernels this object holds; kShadeMedia's are path_media.hip's (ctl::media_launch_*)
+// the levels whose path kernels this object holds; kShadeMedia's are path_media.hip's (ctl::media_launch_*),
+// kShadeSensors' path_sensors.hip's (ctl::sensors_launch_*)
 #define CTL_PATH_LEVELS_HERE kShadeLean, kShadeFull, kShadeEnv, kShadeAlpha, kShadeMat, kShadeLights
 
 namespace {
@@ -266,22 +267,7 @@ __global__ __launch_bounds__(kBlock) void camera_ray_kernel(DevScene S_arg, Path
                                                             uint64_t items, ctl_ray* rays) {
     const DevScene& S = kernarg_ref<DevScene>(S_arg, 0);   // read in place (common.h kernarg_ref)
     const PathParams& P = kernarg_ref<PathParams>(P_arg, kernarg_next<DevScene, PathParams>(0));
-    const uint64_t g = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (g >= items) return;
-    uint32_t px, py;
-    float4 o4 = make_float4(0.0f, 0.0f, 0.0f, S.ray_eps), d4 = make_float4(0.0f, 0.0f, 1.0f, 0.0f);
-    if (work_pixel(P, g, px, py)) {
-        const uint32_t idx = py * P.width + px;
-        SamplerDev rng;
-        rng.init(s1, s2, P.nseq, P.len, idx);
-        f3 o, d;
-        (void)primary_ray(S, rng, px, py, o, d);
-        o4 = make_float4(o.x, o.y, o.z, S.ray_eps);
-        d4 = make_float4(d.x, d.y, d.z, FLT_MAX);
-    }
-    float4* r4 = reinterpret_cast<float4*>(rays + g);
-    r4[0] = o4;
-    r4[1] = d4;
+    camera_ray_item<kShadeLean>(S, P, s1, s2, items, rays);   // path_kernels.h
 }
 
 // Batch KernelDynamicScene::Occluded(Ray(o, d), 0, tmax) (KernelDynamicScene.cu:70-80),
@@ -572,7 +558,8 @@ static ctl_status launch_schedule(ctl_ctx* c, const ctl_pt_params* p, const Path
     const uint64_t want = (threads + kBlock - 1) / kBlock;
     const bool known = launch_path<CTL_PATH_LEVELS_HERE>(c, persistent, stats, P, s1, s2, threads, want, grid, cursor, fb,
                                                          PS, tbl, s) ||
-                       ctl::media_launch_path(c, persistent, stats, P, s1, s2, threads, want, grid, cursor, fb, PS, tbl, s);
+                       ctl::media_launch_path(c, persistent, stats, P, s1, s2, threads, want, grid, cursor, fb, PS, tbl, s) ||
+                       ctl::sensors_launch_path(c, persistent, stats, P, s1, s2, threads, want, grid, cursor, fb, PS, tbl, s);
     assert(known);
     (void)known;
     CTL_HIP(c, hipGetLastError());
@@ -924,7 +911,8 @@ CTL_API ctl_status ctl_render_pass_blocks(ctl_ctx* c, const ctl_pt_params* p, co
     const float2* s2 = c->d_s2[c->active];
     const uint32_t* own_tbl = c->d_block_tbl.get();
     const bool known = launch_path_blocks<CTL_PATH_LEVELS_HERE>(c, P, s1, s2, items, want, cursor, PS, own_tbl, s) ||
-                       ctl::media_launch_blocks(c, P, s1, s2, items, want, cursor, PS, own_tbl, s);
+                       ctl::media_launch_blocks(c, P, s1, s2, items, want, cursor, PS, own_tbl, s) ||
+                       ctl::sensors_launch_blocks(c, P, s1, s2, items, want, cursor, PS, own_tbl, s);
     assert(known);
     (void)known;
     CTL_HIP(c, hipGetLastError());
@@ -958,8 +946,10 @@ CTL_API ctl_status ctl_camera_rays(ctl_ctx* c, const ctl_pt_params* params, ctl_
     if (capacity < (int64_t)items) { c->err = "camera_rays: ray buffer too small"; return CTL_ERR_INVALID; }
     CTL_HIP(c, hipSetDevice(c->device));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(camera_ray_kernel, dim3((unsigned)((items + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, c->scene,
-                       P, c->d_s1[c->active], c->d_s2[c->active], items, d_rays);
+    // a scene seen through another sensor than the perspective one: that level's kernel (path_sensors.hip)
+    if (!ctl::sensors_launch_camera_rays(c, P, c->d_s1[c->active], c->d_s2[c->active], items, d_rays, s))
+        hipLaunchKernelGGL(camera_ray_kernel, dim3((unsigned)((items + kBlock - 1) / kBlock)), dim3(kBlock), 0, s,
+                           c->scene, P, c->d_s1[c->active], c->d_s2[c->active], items, d_rays);
     CTL_HIP(c, hipGetLastError());
     return CTL_OK;
 }

@@ -1,10 +1,11 @@
 // path_kernels.h -- the PathTracer's kernel templates (path_kernel, path_kernel_persistent,
 // path_kernel_persistent_blocks, with the path state they park in LDS) and their one launch.
 // Two files include it, each instantiating the levels of its own code object: ctl_trace.hip the
-// levels lean ... lights, path_media.hip kShadeMedia alone.  There are two objects because the
+// levels lean ... lights, path_media.hip kShadeMedia alone, path_sensors.hip kShadeSensors alone.  There are
+// several objects because the
 // inliner's and the interprocedural passes' choices depend on a module's callers: with the media
 // kernels in ctl_trace.hip's object, ten kernels of the levels full, env and alpha changed their
-// spills.  The kernels are in an anonymous namespace at file scope, so each object
+// spills; kShadeSensors follows that rule.  The kernels are in an anonymous namespace at file scope, so each object
 // has its own.  ctl_trace.hip includes this in front of its own kernels (the sampler kernels come
 // behind it): that order compiles every kernel to the code it had when all were in one file.
 #pragma once
@@ -179,7 +180,7 @@ __global__ __launch_bounds__(kBlock) void path_kernel(DevScene S_arg, PathParams
         rng.init(s1, s2, P.nseq, P.len, idx);
         PathCtx<STATS, SINGLE, WIDE, FULL> C{S, P, rng, st, 0, TraceStats{0, 0, 0}, true, PathVars{}};
         f3 o, dw;
-        const f2 pX = primary_ray(S, rng, px, py, o, dw);
+        const f2 pX = primary_ray<FULL>(S, rng, px, py, o, dw);
         if (apron_keep(P, g, pX)) {
             C.v.begin(pX, o, dw);
             while (C.bounce()) {}
@@ -227,6 +228,30 @@ __global__ __launch_bounds__(kBlock) void path_kernel(DevScene S_arg, PathParams
 // default kernels keep their names and code: path_kernel_persistent (ownership
 // tile % num_ranks == rank) and path_kernel_persistent_blocks (the blocks of a
 // list, ctl_render_pass_blocks).
+// One work item of ctl_camera_rays, the body of camera_ray_kernel (ctl_trace.hip) and of camera_ray_sensors_kernel
+// (path_sensors.hip): the path kernels' first ray (primary_ray of the level) as a traversalRay, tmin = scene eps,
+// tmax = FLT_MAX; a work item outside the image gets an empty interval (tmax = 0).  items <= the caller's capacity.
+template <int FULL>
+__device__ __forceinline__ void camera_ray_item(const DevScene& S, const PathParams& P, const float* s1, const float2* s2,
+                                                uint64_t items, ctl_ray* rays) {
+    const uint64_t g = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (g >= items) return;
+    uint32_t px, py;
+    float4 o4 = make_float4(0.0f, 0.0f, 0.0f, S.ray_eps), d4 = make_float4(0.0f, 0.0f, 1.0f, 0.0f);
+    if (work_pixel(P, g, px, py)) {
+        const uint32_t idx = py * P.width + px;
+        SamplerDev rng;
+        rng.init(s1, s2, P.nseq, P.len, idx);
+        f3 o, d;
+        (void)primary_ray<FULL>(S, rng, px, py, o, d);
+        o4 = make_float4(o.x, o.y, o.z, S.ray_eps);
+        d4 = make_float4(d.x, d.y, d.z, FLT_MAX);
+    }
+    float4* r4 = reinterpret_cast<float4*>(rays + g);
+    r4[0] = o4;
+    r4[1] = d4;
+}
+
 #define CTL_PERSIST_KERNEL_ATTRS \
     __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(SINGLE ? (FULL ? CTL_PERSIST_WAVES_FULL : CTL_PERSIST_WAVES) : 2)))
 

@@ -67,7 +67,7 @@
                         rng.d1 = 0; rng.d2 = 0;
                         if constexpr (!kList) *pkw = (int)k;
                         f3 o, dw;
-                        const f2 pX = primary_ray(S, rng, px, py, o, dw);
+                        const f2 pX = primary_ray<FULL>(S, rng, px, py, o, dw);
                         if constexpr (kList) *pkw = (int)(k | landing_code(Pw, px, py, pX) << kListItemBits);
                         v.begin(pX, o, dw);
                         shadowPhase = false;

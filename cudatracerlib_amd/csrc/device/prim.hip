@@ -65,9 +65,20 @@ void prim_kernel(DevScene S_arg, PathParams P_arg, PrimParams Q, const float* s1
         SamplerDev rng;
         rng.init(s1, s2, P.nseq, P.len, idx);
         const f2 pX = mk2((float)px, (float)py);
-        (void)rng.next2();   // aperture sample of sampleRayDifferential (unused by PerspectiveSensor)
         f3 o, d;
-        sensor_ray(S, pX, o, d);
+        // kShadeSensors: the scene's sensor (ctl_sensor.h) takes the aperture sample; rayX and rayY are kept for the
+        // first hit's partials and the environment's footprint (a spherical sensor defines none: no partials, and
+        // the footprint of the ray itself)
+        f3 soX = mk3s(0.0f), sdX = mk3s(0.0f), soY = mk3s(0.0f), sdY = mk3s(0.0f);
+        bool sdiff = false;
+        if constexpr (CTL_SENSORS_OF(FULL)) {
+            const f2 ap = rng.next2();
+            sdiff = sensor_sample_ray_differential(S.camera, scene_sensor(S), pX, ap, o, d, soX, sdX, soY, sdY);
+            if (!sdiff) { sdX = d; sdY = d; }
+        } else {
+            (void)rng.next2();   // aperture sample of sampleRayDifferential (unused by PerspectiveSensor)
+            sensor_ray(S, pX, o, d);
+        }
         HitRec h = no_hit(FLT_MAX);
         rays++;
         if (S.n_nodes != 0) ok &= trace_one<0, false, SINGLE, WIDE, CTL_ALPHA_OF(FULL)>(S, o, d, 0.0f, S.ray_eps, h, st, &ts);
@@ -85,7 +96,14 @@ void prim_kernel(DevScene S_arg, PathParams P_arg, PrimParams Q, const float* s1
                 HitSurface sf;
                 const ctl_material mat =
                     surface_at<FULL>(S, node, h.tri, mk2(h.u, h.v), o + h.t * d, d, P.half_quirk, dg, b, sf);
-                if (FULL) {
+                if (CTL_SENSORS_OF(FULL)) {
+                    if (sdiff) {
+                        compute_partials(dg, soX, sdX, soY, sdY);
+                    } else {
+                        dg.dudx = dg.dudy = dg.dvdx = dg.dvdy = 0.0f;
+                        dg.has_partials = false;
+                    }
+                } else if (FULL) {
                     f3 co, dX, dY;
                     sensor_diff(S, pX, co, dX, dY);
                     compute_partials(dg, co, dX, co, dY);
@@ -114,7 +132,7 @@ void prim_kernel(DevScene S_arg, PathParams P_arg, PrimParams Q, const float* s1
                     if (mat.node_light_index != 0xffffffffu) Le = HitEmitter(S, sf.N, mat).Le(dg, w);
                     // Transmittance(r, 0, prim_res.m_fDist) (PrimTracer.cu:60): 1 without a medium
                     spec through = mk3s(1.0f);
-                    if constexpr (CTL_MEDIA_OF(FULL)) through = medium_transmittance(scene_volume(S), o, d, 0.0f, h.t);
+                    if constexpr (CTL_MEDIA_OF(FULL)) through = scene_transmittance<FULL>(S, o, d, 0.0f, h.t);
                     if (Q.mode == CTL_PRIM_FIRST_LE || Q.mode == CTL_PRIM_FIRST_NON_DELTA_LE) {
                         L = through * Le;
                     } else if (Q.mode == CTL_PRIM_FIRST_F || Q.mode == CTL_PRIM_FIRST_NON_DELTA_F) {
@@ -144,9 +162,13 @@ void prim_kernel(DevScene S_arg, PathParams P_arg, PrimParams Q, const float* s1
         else if (CTL_ENV_OF(FULL) && S.env_index != 0xffffffffu) {
             // L = EvalEnvironment(r, rX, rY) (PrimTracer.cu:102): the map filtered
             // over the primary ray's differential footprint
-            f3 co, dX, dY;
-            sensor_diff(S, pX, co, dX, dY);
-            L = env_eval_diff(env_view(S), d, dX, dY);
+            if constexpr (CTL_SENSORS_OF(FULL)) {
+                L = env_eval_diff(env_view(S), d, sdX, sdY);
+            } else {
+                f3 co, dX, dY;
+                sensor_diff(S, pX, co, dX, dY);
+                L = env_eval_diff(env_view(S), d, dX, dY);
+            }
         }
         add_sample(fb, P, pX, L);   // Image::AddSample((float)x, (float)y, L): the pixel's own entry
         if (Q.write_depth) depth[idx] = depth_d3d(h.t, Q.near_d, Q.far_d);   // g_DepthImage2.Store

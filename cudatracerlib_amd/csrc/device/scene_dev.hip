@@ -182,6 +182,9 @@ ctl_status validate(ctl_ctx* c, const ctl_scene_desc* d, uint32_t dirty) {
             }
         }
     }
+    // the sensor record is a scene constant: checked on every upload and update
+    if (d->sensor)
+        if (const char* why = sensor_check(*d->sensor)) { c->err = std::string("scene_upload: ") + why; return CTL_ERR_INVALID; }
     if (dirty & CTL_DIRTY_VOLUMES) {
         // one medium at most: the reference's choice among several has no defined behaviour (ctl_trace.h)
         if (d->n_volumes > 1) { c->err = "scene_upload: more than one volume"; return CTL_ERR_INVALID; }
@@ -381,8 +384,11 @@ ctl_status commit_arrays(ctl_ctx* c, const ctl_scene_desc* d, uint32_t dirty, hi
 // belong to the epoch they were rendered in.  P: plan_trees of this commit.
 ctl_status commit(ctl_ctx* c, const ctl_scene_desc* d, uint32_t dirty, hipStream_t s, TreePlan& P) {
     DevScene before = c->scene;
+    const ctl_sensor sensor_before = c->h_sensor;   // a constant kept beside DevScene (traverse.h scene_sensor)
     const ctl_status r = commit_arrays(c, d, dirty, s, P);
-    if (r != CTL_OK || dirty != 0 || std::memcmp(&before, &c->scene, sizeof(DevScene)) != 0) c->scene_epoch++;
+    if (r != CTL_OK || dirty != 0 || std::memcmp(&before, &c->scene, sizeof(DevScene)) != 0 ||
+        std::memcmp(&sensor_before, &c->h_sensor, sizeof(ctl_sensor)) != 0)
+        c->scene_epoch++;
     return r;
 }
 
@@ -421,6 +427,12 @@ ctl_status commit_arrays(ctl_ctx* c, const ctl_scene_desc* d, uint32_t dirty, hi
         if (dirty & CTL_DIRTY_VOLUMES) c->h_volume = d->n_volumes ? d->volumes[0] : ctl_volume{};
         if (dirty & CTL_DIRTY_VOLUMES) c->d_volume = d->n_volumes ? reinterpret_cast<const ctl_volume*>(at) : nullptr;
         SD_HIP(c, hipMemcpyAsync(at, &c->h_volume, sizeof(ctl_volume), hipMemcpyHostToDevice, s));   // h_volume outlives it
+    }
+    {
+        // the sensor record behind it (traverse.h scene_sensor): one of the scene constants, written on every commit
+        c->h_sensor = d->sensor ? *d->sensor : sensor_default();
+        SD_HIP(c, hipMemcpyAsync(c->sarr[SA_LIGHTS].mem.get() + kSensorAt, &c->h_sensor, sizeof(ctl_sensor),
+                                 hipMemcpyHostToDevice, s));   // h_sensor outlives it
     }
     PUT(CTL_DIRTY_LIGHTS, SA_LTRIS, d->light_tris, d->n_light_tris, ctl_light_tri, 0);
     PUT(CTL_DIRTY_LIGHTS, SA_LCDF, d->light_tri_cdf, d->n_light_tri_cdf, float, 0);
@@ -541,9 +553,10 @@ ctl_status commit_arrays(ctl_ctx* c, const ctl_scene_desc* d, uint32_t dirty, hi
         for (uint32_t i = 0; i < d->n_lights; i++)
             if (light_is_delta(d->lights[i].kind)) c->has_delta_light = true;
     }
-    // the scene's level (dispatch.h scene_level); adding or removing the volume (CTL_DIRTY_VOLUMES)
-    // changes it here, with no tree work
-    S.full_shading = (uint32_t)scene_level((int)c->material_level, c->has_delta_light, c->d_volume != nullptr);
+    // the scene's level (dispatch.h scene_level); adding or removing the volume (CTL_DIRTY_VOLUMES), or
+    // another sensor type (any update), changes it here, with no tree work
+    S.full_shading = (uint32_t)scene_level((int)c->material_level, c->has_delta_light, c->d_volume != nullptr,
+                                           c->h_sensor.type != CTL_SENSOR_PERSPECTIVE);
     if (dirty & (CTL_DIRTY_NODES | CTL_DIRTY_MESHES | CTL_DIRTY_BVH)) {
         S.n_nodes = d->n_nodes;
         S.start_node = d->scene_start_node;
@@ -602,6 +615,7 @@ void free_scene(ctl_ctx* c) {
     c->has_delta_light = false;
     c->d_volume = nullptr;
     c->h_volume = ctl_volume{};
+    c->h_sensor = sensor_default();
     c->h_wbase.clear();
     c->tree_flags = 0xffffffffu;
     c->device_eps = false;

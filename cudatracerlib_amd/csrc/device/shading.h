@@ -57,13 +57,38 @@ __device__ __forceinline__ void sensor_diff(const DevScene& S, f2 pX, f3& o, f3&
 }
 
 // Sensor sample + primary ray of pixel (px, py) (pathKernel2, PathTracer.cu:182-194;
-// PerspectiveSensor::sampleRayDifferential, Sensor.cu:130-144).
+// PerspectiveSensor::sampleRayDifferential, Sensor.cu:130-144).  At kShadeSensors the scene's sensor
+// (ctl_sensor.h; rayX and rayY are taken at the first hit, sensor_partials) consumes the aperture
+// sample every other level draws and discards: the same draws in the same order.
+template <int FULL = kShadeLean>
 __device__ __forceinline__ f2 primary_ray(const DevScene& S, SamplerDev& rng, uint32_t px, uint32_t py, f3& o,
                                           f3& dw) {
     f2 pX = mk2((float)px, (float)py) + rng.next2();
-    (void)rng.next2();   // aperture sample (unused by PerspectiveSensor)
-    sensor_ray(S, pX, o, dw);
+    if constexpr (level_sensors(FULL)) {
+        const f2 ap = rng.next2();
+        f3 oX, dX, oY, dY;
+        (void)sensor_sample_ray_differential(S.camera, scene_sensor(S), pX, ap, o, dw, oX, dX, oY, dY);
+    } else {
+        (void)rng.next2();   // aperture sample (unused by PerspectiveSensor)
+        sensor_ray(S, pX, o, dw);
+    }
     return pX;
+}
+
+// kShadeSensors: bRec.dg.computePartials(r, rX, rY) at the path's first hit with the scene's sensor.  rayX and rayY
+// depend on the aperture sample, which is not carried with the path: it is the path's 2-D draw kApertureDraw, read
+// again from the tables.  false (the spherical sensor, ctl_sensor.h): the path has no UV partials.
+constexpr uint32_t kApertureDraw = 1;   // draw 0 is the pixel jitter
+__device__ __forceinline__ bool sensor_partials(const DevScene& S, f2 pX, f2 ap, dgeom& dg) {
+    f3 o, d, oX, dX, oY, dY;
+    const bool has = sensor_sample_ray_differential(S.camera, scene_sensor(S), pX, ap, o, d, oX, dX, oY, dY);
+    if (has) {
+        compute_partials(dg, oX, dX, oY, dY);
+    } else {
+        dg.dudx = dg.dudy = dg.dvdx = dg.dvdy = 0.0f;
+        dg.has_partials = false;
+    }
+    return has;
 }
 
 // Shading level of the path kernels (template FULL, DevScene::full_shading): lean = constant diffuse materials only;
@@ -80,6 +105,9 @@ __device__ __forceinline__ f2 primary_ray(const DevScene& S, SamplerDev& rng, ui
 // media = lights plus one homogeneous participating medium (ctl_medium.h): the medium step in front of the split
 // into miss and hit, the attenuated light sample, the escaped-path term after a medium interaction.  A scene with a
 // volume runs this level, every other scene the instantiations it ran before.
+// sensors = media plus the sensor switch (ctl_sensor.h): the primary ray and the first hit's ray differentials come
+// from the scene's thin-lens, orthographic, telecentric or spherical sensor.  A scene seen through another sensor
+// than the perspective one runs this level, every other scene the instantiations it ran before.
 // The levels, what each carries and which one a scene runs are dispatch.h's table and scene_level; the
 // names below read that table: the traversal's ALPHA flag of a level, the levels that carry the environment
 // light, the seven-type BSDF dispatch, the delta lights and the medium, and the instantiation the kernels
@@ -89,22 +117,24 @@ __device__ __forceinline__ f2 primary_ray(const DevScene& S, SamplerDev& rng, ui
 #define CTL_EXT_OF(F) (ctl::level_ext(F))
 #define CTL_DELTA_LIGHTS_OF(F) (ctl::level_delta_lights(F))
 #define CTL_MEDIA_OF(F) (ctl::level_media(F))
+#define CTL_SENSORS_OF(F) (ctl::level_sensors(F))
 #define CTL_NO_TRACE_LEVEL(F) (ctl::level_no_trace(F))
-// Host: f(FU) with DevScene::full_shading as a constant (dispatch.h), over the seven levels or, for the
-// kernels that never trace, the six they instantiate.  full_shading only ever holds one of the seven
+// Host: f(FU) with DevScene::full_shading as a constant (dispatch.h), over the eight levels or, for the
+// kernels that never trace, the seven they instantiate.  full_shading only ever holds one of the eight
 // (scene_dev.hip).  The PathTracer's kernels have their lists at their launch (path_kernels.h): the levels
-// of ctl_trace.hip's code object and of path_media.hip's.
+// of ctl_trace.hip's code object, of path_media.hip's and of path_sensors.hip's.
 template <class F>
 void with_shade_level(uint32_t full, F&& f) {
     const bool known =
-        with_level<kShadeLean, kShadeFull, kShadeEnv, kShadeAlpha, kShadeMat, kShadeLights, kShadeMedia>((int)full, f);
+        with_level<kShadeLean, kShadeFull, kShadeEnv, kShadeAlpha, kShadeMat, kShadeLights, kShadeMedia, kShadeSensors>((int)full, f);
     assert(known);
     (void)known;
 }
 template <class F>
 void with_no_trace_level(uint32_t full, F&& f) {
     const bool known =
-        with_level<kShadeLean, kShadeFull, kShadeEnv, kShadeMat, kShadeLights, kShadeMedia>(CTL_NO_TRACE_LEVEL((int)full), f);
+        with_level<kShadeLean, kShadeFull, kShadeEnv, kShadeMat, kShadeLights, kShadeMedia, kShadeSensors>(
+            CTL_NO_TRACE_LEVEL((int)full), f);
     assert(known);
     (void)known;
 }
@@ -219,6 +249,15 @@ __device__ __forceinline__ spec env_miss(const DevScene& S, const PathParams& P,
     return (v.cf * misWeight) * env_eval(E, v.rdir);
 }
 
+// Transmittance(ray, t0, t1) of the scene's medium (kShadeMedia and above).  kShadeSensors also runs scenes
+// without a medium, whose record is all zero (kind 0): there the factor is the 1 the lower levels multiply by.
+template <int FULL>
+__device__ __forceinline__ spec scene_transmittance(const DevScene& S, f3 o, f3 d, float t0, float t1) {
+    const ctl_volume& V = scene_volume(S);
+    if constexpr (CTL_SENSORS_OF(FULL)) { if (V.kind == 0) return mk3s(1.0f); }
+    return medium_transmittance(V, o, d, t0, t1);
+}
+
 // UniformSampleOneLight up to its occlusion test (TraceAlgorithms.cu:44-73, 92-101; needs S.n_lights > 0): draws the
 // light choice and the light position, and when both the light sample and the BSDF value are non-zero fills the
 // shadow ray and, in sh.add, EstimateDirect(...) / pdf -- the value UniformSampleOneLight returns when the shadow
@@ -248,7 +287,7 @@ __device__ __forceinline__ void nee_sample(const DevScene& S, SamplerDev& rng, c
             if (dRec.measure != kEDiscrete)
                 weight = power_heuristic(dRec.pdf * lpdf, FULL ? bsdf_pdf<CTL_EXT_OF(FULL)>(mat, b2, gm, ge) : diffuse_pdf(mat, b2));
             spec ret = value * bsdfVal * weight;
-            if constexpr (ATT) ret = ret * medium_transmittance(scene_volume(S), dRec.ref, dRec.d, 0.0f, dRec.dist);
+            if constexpr (ATT) ret = ret * scene_transmittance<FULL>(S, dRec.ref, dRec.d, 0.0f, dRec.dist);
             else ret = ret * mk3s(1.0f);
             sh.valid = true;
             sh.d = dRec.d;
@@ -277,6 +316,8 @@ __device__ __forceinline__ int medium_step(const DevScene& S, const PathParams& 
                                            const HitRec& h, ShadowReq& sh) {
     sh.valid = false;
     const ctl_volume& V = scene_volume(S);   // one record for every lane, at a kernel-uniform address
+    // kShadeSensors also runs scenes without a medium (an all-zero record): no interaction, no draw
+    if constexpr (CTL_SENSORS_OF(FULL)) { if (V.kind == 0) return kMediumNone; }
     float minT, maxT;
     if (!medium_intersect(V, v.rori, v.rdir, 0.0f, h.t, minT, maxT)) return kMediumNone;
     medium_rec m;
@@ -372,15 +413,20 @@ __device__ __forceinline__ bool shade_hit(const DevScene& S, const PathParams& P
     if (FULL) {
         if (v.depth == 1) {   // bRec.dg.computePartials(r, rX, rY) (PathTracer.cu:60-61)
             if constexpr (kLazy) pk->load_px(v);
-            f3 co, dX, dY;
-            sensor_diff(S, v.pX, co, dX, dY);
-            compute_partials(dg, co, dX, co, dY);
+            bool has = true;   // kShadeSensors: the sensor defines rayX and rayY (sensor_partials)
+            if constexpr (CTL_SENSORS_OF(FULL)) {
+                has = sensor_partials(S, v.pX, rng.peek2(kApertureDraw), dg);
+            } else {
+                f3 co, dX, dY;
+                sensor_diff(S, v.pX, co, dX, dY);
+                compute_partials(dg, co, dX, co, dY);
+            }
             if (part) {
                 *part = make_float4(dg.dudx, dg.dudy, dg.dvdx, dg.dvdy);
-                if constexpr (CTL_MEDIA_OF(FULL)) v.has_partials = true;
+                if constexpr (CTL_MEDIA_OF(FULL)) v.has_partials = has;
             } else {
                 v.dudx = dg.dudx; v.dudy = dg.dudy; v.dvdx = dg.dvdx; v.dvdy = dg.dvdy;
-                v.has_partials = true;
+                v.has_partials = has;
             }
         } else if (part) {
             // kShadeMedia: a path whose depth-1 event was a medium interaction meets its first surface here with

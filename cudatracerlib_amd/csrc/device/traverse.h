@@ -95,7 +95,7 @@ struct DevScene {
     const float4* scene_bvh;    // instance BVH
     const float4* xf;           // node transforms, 4 float4 rows each
     const float4* inv_xf;
-    const ctl_light* lights;    // CTL_MAX_NUM_LIGHTS slots, then the scene's ctl_volume (scene_volume below)
+    const ctl_light* lights;    // CTL_MAX_NUM_LIGHTS slots, then the scene's ctl_volume and ctl_sensor (scene_volume, scene_sensor below)
     const ctl_light_tri* light_tris;
     const float* light_tri_cdf;
     const float4* normal_lut;   // 65536 decoded spherical normals (Compression.h:20-31)
@@ -119,7 +119,7 @@ struct DevScene {
     const float4* scene_wbvh;    // instance-level wide nodes
     const uint32_t* mesh_wbase;  // first wide node of each mesh
     uint32_t wide;               // wide trees present (scene flag CTL_SCENE_BINARY_BVH clear)
-    uint32_t full_shading;       // shading level of the path kernels: kShadeLean .. kShadeMedia
+    uint32_t full_shading;       // shading level of the path kernels: kShadeLean .. kShadeSensors
     uint32_t alpha;              // KernelDynamicScene::doAlphaMapping (some material has an alpha map)
     uint32_t s_wnode_base;
     uint32_t quant;              // wide trees in the 64-B quantized format (ctl_qnode.h)
@@ -135,6 +135,13 @@ struct DevScene {
 // kernel, whose size moves the arguments after it -- is what it was before the level existed.
 __device__ __forceinline__ const ctl_volume& scene_volume(const DevScene& S) {
     return *reinterpret_cast<const ctl_volume*>(S.lights + CTL_MAX_NUM_LIGHTS);   // common.h kVolumeAt
+}
+
+// The scene's sensor record (ctl_sensor.h), read by the kShadeSensors kernels only: behind the volume
+// record, for the same reason.  One record for every lane at a kernel-uniform address: scalar loads.
+__device__ __forceinline__ const ctl_sensor& scene_sensor(const DevScene& S) {
+    return *reinterpret_cast<const ctl_sensor*>(reinterpret_cast<const char*>(S.lights + CTL_MAX_NUM_LIGHTS) +
+                                                sizeof(ctl_volume));   // common.h kSensorAt
 }
 
 // Index into mats of a triangle's material in node `node` (TraceResult.cu:16-20): its slot + the node's offset

@@ -44,10 +44,11 @@ __device__ __forceinline__ void wf_store(const PathParams& P, const SampleSlots&
     store_sample(P, SS, 0, i, px, py, pX, col);
 }
 
-__global__ __launch_bounds__(kBlock) void wf_gen_kernel(DevScene S_arg, PathParams P_arg, const float* s1, const float2* s2,
-                                                        WfState W, uint64_t n_items, SampleSlots SS) {
-    const DevScene& S = kernarg_ref<DevScene>(S_arg, 0);   // read in place (common.h kernarg_ref)
-    const PathParams& P = kernarg_ref<PathParams>(P_arg, kernarg_next<DevScene, PathParams>(0));
+// The camera stage, the body of wf_gen_kernel and of wf_gen_sensors_kernel (FULL = kShadeSensors: the scene's
+// sensor, shading.h primary_ray)
+template <int FULL>
+__device__ __forceinline__ void wf_gen(const DevScene& S, const PathParams& P, const float* s1, const float2* s2,
+                                       const WfState& W, uint64_t n_items, const SampleSlots& SS) {
     for (uint64_t g = (uint64_t)blockIdx.x * kBlock + threadIdx.x;; g += (uint64_t)gridDim.x * kBlock) {
         // keep whole waves in the loop so the ballot in queue_push sees every lane
         const bool inRange = g < n_items;
@@ -60,9 +61,7 @@ __global__ __launch_bounds__(kBlock) void wf_gen_kernel(DevScene S_arg, PathPara
         if (valid) {
             SamplerDev rng;
             rng.init(s1, s2, P.nseq, P.len, idx);
-            pX = mk2((float)px, (float)py) + rng.next2();
-            (void)rng.next2();   // aperture sample
-            sensor_ray(S, pX, o, d);
+            pX = primary_ray<FULL>(S, rng, px, py, o, d);   // pixel jitter, aperture sample, sensor
             valid = apron_keep(P, g, pX);   // an apron path landing outside the tile: no sample (slot stays 0)
         }
         const bool live = valid && P.max_path_length > 0;
@@ -80,6 +79,21 @@ __global__ __launch_bounds__(kBlock) void wf_gen_kernel(DevScene S_arg, PathPara
             W.meta[i] = make_uint4(idx, 0u | (2u << 16), 1u, 0u);   // d1=0, d2=2, depth=1 (while(depth++ < max))
         }
     }
+}
+
+__global__ __launch_bounds__(kBlock) void wf_gen_kernel(DevScene S_arg, PathParams P_arg, const float* s1, const float2* s2,
+                                                        WfState W, uint64_t n_items, SampleSlots SS) {
+    const DevScene& S = kernarg_ref<DevScene>(S_arg, 0);   // read in place (common.h kernarg_ref)
+    const PathParams& P = kernarg_ref<PathParams>(P_arg, kernarg_next<DevScene, PathParams>(0));
+    wf_gen<kShadeLean>(S, P, s1, s2, W, n_items, SS);
+}
+
+__global__ __launch_bounds__(kBlock) void wf_gen_sensors_kernel(DevScene S_arg, PathParams P_arg, const float* s1,
+                                                                const float2* s2, WfState W, uint64_t n_items,
+                                                                SampleSlots SS) {
+    const DevScene& S = kernarg_ref<DevScene>(S_arg, 0);   // read in place (common.h kernarg_ref)
+    const PathParams& P = kernarg_ref<PathParams>(P_arg, kernarg_next<DevScene, PathParams>(0));
+    wf_gen<kShadeSensors>(S, P, s1, s2, W, n_items, SS);
 }
 
 // Persistent trace over a queue: MODE 0 = extension rays (closest hit),
@@ -348,7 +362,10 @@ int wavefront_pass(ctl_ctx* c, const PathParams& P, const SampleSlots& SS, bool 
         c->err = "wavefront: memset failed";
         return CTL_ERR_HIP;
     }
-    hipLaunchKernelGGL(wf_gen_kernel, dim3(genBlocks), dim3(kBlock), 0, s, c->scene, P, s1, s2, W, items, SS);
+    if (CTL_SENSORS_OF((int)c->scene.full_shading))
+        hipLaunchKernelGGL(wf_gen_sensors_kernel, dim3(genBlocks), dim3(kBlock), 0, s, c->scene, P, s1, s2, W, items, SS);
+    else
+        hipLaunchKernelGGL(wf_gen_kernel, dim3(genBlocks), dim3(kBlock), 0, s, c->scene, P, s1, s2, W, items, SS);
     const int maxB = std::min(P.max_path_length, kMaxBounces);
     uint32_t* cursors = W.counts + 2 * (kMaxBounces + 2);
     for (int b = 0; b < maxB; b++) {

@@ -92,9 +92,10 @@ __device__ __forceinline__ ctl_ray make_ray(f3 o, float tmin, f3 d, float tmax) 
 
 // pathCreateKernelWPT (WavefrontPathTracer.cu:17-49) with one sample per pixel:
 // the payload slot of pixel i is i (rayidx order).
-__global__ __launch_bounds__(kBlock) void wpt_create_kernel(DevScene S_arg, WptArgs A, const float* s1, const float2* s2,
-                                                            uint32_t n, ctl_ray* rays, WptPay* pay, uint32_t* count0) {
-    const DevScene& S = kernarg_ref<DevScene>(S_arg, 0);   // read in place (common.h kernarg_ref)
+// SENSORS: the scene's sensor through Sensor::sampleRay (ctl_sensor.h), which the aperture sample feeds
+template <bool SENSORS>
+__device__ __forceinline__ void wpt_create(const DevScene& S, const WptArgs& A, const float* s1, const float2* s2,
+                                           uint32_t n, ctl_ray* rays, WptPay* pay, uint32_t* count0) {
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
     if (i == 0) { count0[0] = n; count0[1] = 0u; }   // bounce 0: every pixel, no shadow rays
     if (i >= n) return;
@@ -102,9 +103,14 @@ __global__ __launch_bounds__(kBlock) void wpt_create_kernel(DevScene S_arg, WptA
     SamplerDev rng = wpt_rng(s1, s2, A, i, 0);
     // sampleSensorRay(r, Vec2f(x, y) + rng.randomFloat2(), rng.randomFloat2()): arguments left to right
     const f2 pX = mk2((float)x, (float)y) + rng.next2();
-    (void)rng.next2();
     f3 o, d;
-    sensor_ray(S, pX, o, d);
+    if constexpr (SENSORS) {
+        const f2 ap = rng.next2();
+        sensor_sample_ray(S.camera, scene_sensor(S), pX, ap, o, d);
+    } else {
+        (void)rng.next2();
+        sensor_ray(S, pX, o, d);
+    }
     rays[i] = make_ray(o, S.ray_eps, d, FLT_MAX);
     WptPay p;
     p.a = make_float4(1.0f, 1.0f, 1.0f, 0.0f);   // throughput = W = Spectrum(1) (Sensor.cu:117)
@@ -112,6 +118,19 @@ __global__ __launch_bounds__(kBlock) void wpt_create_kernel(DevScene S_arg, WptA
     p.c = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float((uint32_t)half_round_int(x) | ((uint32_t)half_round_int(y) << 16)));
     p.d = make_uint4(0xffffffffu, 1u, 0u, i);
     pay[i] = p;
+}
+
+__global__ __launch_bounds__(kBlock) void wpt_create_kernel(DevScene S_arg, WptArgs A, const float* s1, const float2* s2,
+                                                            uint32_t n, ctl_ray* rays, WptPay* pay, uint32_t* count0) {
+    const DevScene& S = kernarg_ref<DevScene>(S_arg, 0);   // read in place (common.h kernarg_ref)
+    wpt_create<false>(S, A, s1, s2, n, rays, pay, count0);
+}
+
+__global__ __launch_bounds__(kBlock) void wpt_create_sensors_kernel(DevScene S_arg, WptArgs A, const float* s1,
+                                                                    const float2* s2, uint32_t n, ctl_ray* rays,
+                                                                    WptPay* pay, uint32_t* count0) {
+    const DevScene& S = kernarg_ref<DevScene>(S_arg, 0);   // read in place (common.h kernarg_ref)
+    wpt_create<true>(S, A, s1, s2, n, rays, pay, count0);
 }
 
 // pathIterateKernel<NEXT_EVENT_EST> body for payload element j (WavefrontPathTracer.cu:56-148).
@@ -458,8 +477,12 @@ int wpt_pass(ctl_ctx* c, const ctl_wpt_params* prm, ctl_pixel* fb, hipStream_t s
     uint32_t* const h_counts = B->h_cnt[hb].get();
     const uint32_t n0 = (uint32_t)items;
     int cur = 0;
-    hipLaunchKernelGGL(wpt_create_kernel, dim3(nb_max), dim3(kBlock), 0, s, c->scene, A, s1, s2, n0, B->rays[0],
-                       B->pay[0], B->counts.get());
+    if (CTL_SENSORS_OF((int)c->scene.full_shading))
+        hipLaunchKernelGGL(wpt_create_sensors_kernel, dim3(nb_max), dim3(kBlock), 0, s, c->scene, A, s1, s2, n0,
+                           B->rays[0], B->pay[0], B->counts.get());
+    else
+        hipLaunchKernelGGL(wpt_create_kernel, dim3(nb_max), dim3(kBlock), 0, s, c->scene, A, s1, s2, n0, B->rays[0],
+                           B->pay[0], B->counts.get());
     WPT_HIP(hipGetLastError());
     // The queue sizes stay on the device: every kernel of bounce b reads slot b,
     // the grids are sized for the largest queue (the pass's pixels) and idle

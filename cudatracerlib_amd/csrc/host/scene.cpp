@@ -11,6 +11,7 @@
 #include "../ctl_env.h"
 #include "../ctl_light.h"
 #include "../ctl_medium.h"
+#include "../ctl_sensor.h"
 #include "bvh_build.h"
 #include "ref_split.h"
 #include "../ctl_shade.h"
@@ -33,7 +34,7 @@ void woop_set(f3 a, f3 b, f3 c, ctl_woop_tri& out) { woop_set_hd(a, b, c, out.v)
 void woop_get(const ctl_woop_tri& in, f3& v0, f3& v1, f3& v2) { woop_get_hd(in.v, v0, v1, v2); }
 
 void camera_setup(const float pos[3], const float tar[3], const float up[3], float fov_deg, float nearc, float farc,
-                  uint32_t w, uint32_t h, ctl_camera& out) {
+                  uint32_t w, uint32_t h, ctl_camera& out, uint32_t sensor_type) {
     f3 p = mk3(pos[0], pos[1], pos[2]), t = mk3(tar[0], tar[1], tar[2]), u = mk3(up[0], up[1], up[2]);
     f3 f = normalize(t - p);
     f3 r = normalize(cross(f, u));
@@ -44,19 +45,10 @@ void camera_setup(const float pos[3], const float tar[3], const float up[3], flo
     m44 toWorld = matmul(tr, view);                                  // Translate(pos) % rot
     float resx = (float)w, resy = (float)h;
     float invx = 1.0f / resx, invy = 1.0f / resy;                    // Vec2f(1) / m_resolution
-    float aspect = resx / resy;
     float fov = ((float)CTL_PI / 180.f) * fov_deg;                   // math::Radians
-    m44 sc = m44_identity(); sc.at(0, 0) = -0.5f; sc.at(1, 1) = -0.5f * aspect; sc.at(2, 2) = 1.0f;
-    m44 tl = m44_identity(); tl.at(0, 3) = -1.0f; tl.at(1, 3) = -1.0f / aspect; tl.at(2, 3) = 0.0f;
-    float recip = 1.0f / (farc - nearc);                             // float4x4::Perspective
-    float cot = 1.0f / cr_tan(fov / 2.0f);
-    m44 pe = m44_zero();
-    pe.at(0, 0) = cot; pe.at(1, 1) = cot; pe.at(2, 2) = farc * recip; pe.at(2, 3) = -nearc * farc * recip;
-    pe.at(3, 2) = 1;
-    m44 c2s = matmul(matmul(sc, tl), pe);
-    m44 s2c = inverse(c2s);
-    f3 dx = xform_point(s2c, mk3(invx, 0.0f, 0.0f)) - xform_point(s2c, mk3s(0.0f));
-    f3 dy = xform_point(s2c, mk3(0.0f, invy, 0.0f)) - xform_point(s2c, mk3s(0.0f));
+    m44 s2c;
+    f3 dx, dy;
+    sensor_update(sensor_type, fov, nearc, farc, resx, resy, s2c, dx, dy);   // the type's Update() (ctl_sensor.h)
     memcpy(out.to_world.m, toWorld.d, 64);
     memcpy(out.sample_to_camera.m, s2c.d, 64);
     out.dx[0] = dx.x; out.dx[1] = dx.y; out.dx[2] = dx.z;
@@ -300,6 +292,30 @@ CTL_API ctl_status ctl_host_scene_set_camera(ctl_host_scene* s, const float pos[
     s->cam_fov = fov_deg; s->cam_near = near_clip; s->cam_far = far_clip;
     s->cam_w = width; s->cam_h = height;
     s->has_camera = true;
+    return CTL_OK;
+}
+
+CTL_API ctl_status ctl_host_scene_set_sensor(ctl_host_scene* s, uint32_t type, float aperture_radius, float focus_distance,
+                                             const float screen_scale[2]) {
+    if (!s) { set_host_error("set_sensor: null scene"); return CTL_ERR_INVALID; }
+    if (!s->has_camera) { set_host_error("set_sensor: call ctl_host_scene_set_camera first"); return CTL_ERR_STATE; }
+    ctl_sensor R = sensor_default();
+    R.type = type;
+    R.aperture_radius = aperture_radius;
+    R.focus_distance = focus_distance;
+    if (screen_scale) { R.screen_scale[0] = screen_scale[0]; R.screen_scale[1] = screen_scale[1]; }
+    if (const char* why = sensor_check(R)) { set_host_error(std::string("set_sensor: ") + why); return CTL_ERR_INVALID; }
+    s->sensor = R;
+    s->has_sensor = true;
+    return CTL_OK;
+}
+
+CTL_API ctl_status ctl_host_scene_sensor_state(const ctl_host_scene* s, ctl_camera* camera, ctl_sensor* sensor) {
+    if (!s || !camera || !sensor) { set_host_error("sensor_state: null argument"); return CTL_ERR_INVALID; }
+    if (!s->has_camera) { set_host_error("sensor_state: no camera"); return CTL_ERR_STATE; }
+    *sensor = s->has_sensor ? s->sensor : sensor_default();
+    camera_setup(s->cam_pos, s->cam_tar, s->cam_up, s->cam_fov, s->cam_near, s->cam_far, s->cam_w, s->cam_h, *camera,
+                 sensor->type);
     return CTL_OK;
 }
 
@@ -816,7 +832,11 @@ CTL_API ctl_status ctl_host_scene_compile(ctl_host_scene* s, uint32_t threads, c
     for (int k = 0; k < 3; k++) { d.box_min[k] = sceneBox.lo[k]; d.box_max[k] = sceneBox.hi[k]; }
     f3 size = mk3(sceneBox.hi[0] - sceneBox.lo[0], sceneBox.hi[1] - sceneBox.lo[1], sceneBox.hi[2] - sceneBox.lo[2]);
     d.ray_eps = 1e-4f * length(size);   // MIN_RAYTRACE_DISTANCE_RELATIVE * |box|
-    camera_setup(s->cam_pos, s->cam_tar, s->cam_up, s->cam_fov, s->cam_near, s->cam_far, s->cam_w, s->cam_h, d.camera);
+    // the sensor: the type's Update() (ctl_sensor.h sensor_update); no record without ctl_host_scene_set_sensor
+    s->ksensor = s->has_sensor ? s->sensor : sensor_default();
+    camera_setup(s->cam_pos, s->cam_tar, s->cam_up, s->cam_fov, s->cam_near, s->cam_far, s->cam_w, s->cam_h, d.camera,
+                 s->ksensor.type);
+    d.sensor = s->has_sensor ? &s->ksensor : nullptr;
     d.flags = s->flags;
     // the medium: WorldToVolume = VolumeToWorld.inverse() (BaseVolumeRegion::Update)
     s->kvolumes = s->volumes;

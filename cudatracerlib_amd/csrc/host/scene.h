@@ -58,6 +58,9 @@ struct ctl_host_scene {
     bool has_camera = false;
     float cam_pos[3], cam_tar[3], cam_up[3], cam_fov, cam_near, cam_far;
     uint32_t cam_w = 0, cam_h = 0;
+    // ctl_host_scene_set_sensor (without it the PerspectiveSensor and no record); ksensor: the compiled desc's record
+    bool has_sensor = false;
+    ctl_sensor sensor{}, ksensor{};
     uint32_t flags = 0;
     // reference splitting of large triangles before the BVH build (ref_split.h)
     float split_alpha = CTL_DEFAULT_SPLIT_ALPHA;
@@ -104,9 +107,9 @@ namespace ctl {
 void woop_set(f3 a, f3 b, f3 c, ctl_woop_tri& out);
 // TriIntersectorData::getData (Engine/TriIntersectorData.cu:20-32)
 void woop_get(const ctl_woop_tri& in, f3& v0, f3& v1, f3& v2);
-// PerspectiveSensor::Update + Sensor::SetToWorld(pos, tar, up)
+// the sensor type's Update() (ctl_sensor.h sensor_update) + Sensor::SetToWorld(pos, tar, up)
 void camera_setup(const float pos[3], const float tar[3], const float up[3], float fov_deg, float nearc, float farc,
-                  uint32_t w, uint32_t h, ctl_camera& out);
+                  uint32_t w, uint32_t h, ctl_camera& out, uint32_t sensor_type = CTL_SENSOR_PERSPECTIVE);
 void set_host_error(const std::string& s);
 // adds lights to node `node` (area light of material `local_mat`); replaces
 // the radiance when the node already has a light on that material

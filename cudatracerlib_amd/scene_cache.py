@@ -46,6 +46,7 @@ _ARRAYS = {
     "anim_meshes": (_abi.AnimMesh, lambda d: d.n_anim_meshes),
     "materials_ext": (_abi.MaterialExt, lambda d: d.n_materials),
     "volumes": (_abi.Volume, lambda d: d.n_volumes),
+    "sensor": (_abi.Sensor, lambda d: 1),
 }
 
 

@@ -62,7 +62,12 @@ extern "C" {
                                one homogeneous participating medium (ctl_volume, ctl_scene_desc.volumes /
                                n_volumes placed in front of the desc's last member materials_ext, CTL_DIRTY_VOLUMES,
                                ctl_host_scene_add_homogeneous_volume, ctl_medium_eval,
-                               ctl_host_medium_eval) */
+                               ctl_host_medium_eval); the five sensor types (ctl_sensor,
+                               ctl_scene_desc.sensor placed in front of the desc's last member materials_ext,
+                               which moves by 8 bytes: a caller built against an older header must be rebuilt;
+                               ctl_host_scene_set_sensor, ctl_sensor_eval, ctl_host_sensor_eval).  The number
+                               stays 4 as it did for the volume members: ctl_scene_desc's size is what tells
+                               the layouts apart (the scene cache checks it) */
 
 #if defined(_WIN32)
 #define CTL_API __declspec(dllexport)
@@ -341,7 +346,12 @@ typedef struct {
     uint32_t pad[3];
 } ctl_env_light;
 
-/* PerspectiveSensor device state after Update() (SceneTypes/Sensor.cu:76-96). */
+/* The sensor's device state after its type's own Update() (SceneTypes/Sensor.cu):
+ * perspective and thin lens compute sample_to_camera, dx and dy from
+ * float4x4::Perspective(fov, near, far) (:76-96, :226-246), orthographic and
+ * telecentric from float4x4::orthographic(near, far) (:408-427, :515-535); the
+ * spherical sensor reads none of the three.  Without a ctl_sensor record
+ * (ctl_scene_desc.sensor) the sensor is the PerspectiveSensor. */
 typedef struct {
     ctl_float4x4 to_world;          /* SensorBase::toWorld                      */
     ctl_float4x4 sample_to_camera;  /* m_sampleToCamera                         */
@@ -350,6 +360,37 @@ typedef struct {
     float inv_resolution[2];        /* m_invResolution                          */
     uint32_t width, height;
 } ctl_camera;
+
+/* Which of the reference's five sensors (the Sensor aggregate, SceneTypes/Sensor.h:527;
+ * the values are its TYPE_FUNC ids) ctl_camera describes, and what the types
+ * beyond the pinhole add to it.  One of the scene constants: ctl_scene_update
+ * refreshes it on every call, so refocusing or switching the type is an update
+ * with dirty = 0.  Upload and update refuse, naming the field and leaving the
+ * uploaded scene whole: a type outside 1-5; a non-finite or negative
+ * aperture_radius; a non-finite or non-positive focus_distance for types 3 and 5;
+ * a non-finite or non-positive screen_scale for type 5.
+ * sampleRay and sampleRayDifferential of the five types are built (csrc/ctl_sensor.h);
+ * sampleDirect, samplePosition, sampleDirection and the pdfs are not (no integrator
+ * built here calls them), and there is no crop window.
+ * SphericalSensor::sampleRayDifferential writes neither rayX nor rayY, so the
+ * reference computes UV partials from uninitialised rays; here a path under a
+ * spherical sensor carries no UV partials. */
+enum {
+    CTL_SENSOR_SPHERICAL = 1, CTL_SENSOR_PERSPECTIVE = 2, CTL_SENSOR_THINLENS = 3, CTL_SENSOR_ORTHOGRAPHIC = 4,
+    CTL_SENSOR_TELECENTRIC = 5
+};
+typedef struct {
+    uint32_t type;                  /* CTL_SENSOR_*                             */
+    float aperture_radius;          /* m_apertureRadius (types 3, 5)            */
+    float focus_distance;           /* m_focusDistance (types 3, 5)             */
+    float screen_scale[2];          /* screenScale (type 5 reads .x)            */
+    uint32_t pad[3];
+} ctl_sensor;                       /* 32 B */
+#if defined(__cplusplus)
+static_assert(sizeof(ctl_sensor) == 32, "ctl_sensor: 32 B");
+#else
+_Static_assert(sizeof(ctl_sensor) == 32, "ctl_sensor: 32 B");
+#endif
 
 #define CTL_MAX_NUM_LIGHTS 16   /* KernelDynamicScene.h:26 */
 
@@ -482,6 +523,10 @@ typedef struct {
      * materials_ext lies 16 bytes further on.  A caller built against an older header
      * must be rebuilt; its materials_ext would be read as `volumes`.                    */
     const ctl_volume* volumes;          uint32_t n_volumes;
+    /* NULL (the PerspectiveSensor), or the one ctl_sensor record that says which sensor
+     * `camera` describes.  Like volumes it sits in front of materials_ext, which moves
+     * by 8 bytes: a caller built against an older header must be rebuilt.             */
+    const ctl_sensor* sensor;
     /* NULL, or n_materials records parallel to materials[] (BSDF types 6-8) */
     const ctl_material_ext* materials_ext;
 } ctl_scene_desc;
@@ -680,8 +725,8 @@ CTL_API ctl_status ctl_render_pass_blocks(ctl_ctx* ctx, const ctl_pt_params* par
 CTL_API ctl_status ctl_last_pass_ms(ctl_ctx* ctx, float* ms);
 
 /* The primary rays of a pass (what ctl_render_pass traces first: pixel jitter,
- * aperture draw, PerspectiveSensor::sampleRayDifferential, Sensor.cu:130-144)
- * as a traversalRay batch in work order, for ctl_intersect - the camera stage
+ * aperture draw, the uploaded sensor's sampleRayDifferential, Sensor.cu:130-144
+ * for the PerspectiveSensor) as a traversalRay batch in work order, for ctl_intersect - the camera stage
  * of the reference's batch tracers (DoubleRayBuffer callers).  Work items
  * outside the image get tmax = 0.  *n_out = number of rays (owned tiles x
  * tile_size^2); d_rays must hold that many (query with capacity 0). */
@@ -1269,6 +1314,21 @@ CTL_API int32_t ctl_host_scene_add_homogeneous_volume(ctl_host_scene* s, const f
 CTL_API ctl_status ctl_host_scene_set_camera(ctl_host_scene* s, const float pos[3], const float target[3],
                                              const float up[3], float fov_deg, float near_clip,
                                              float far_clip, uint32_t width, uint32_t height);
+/* Which of the reference's five sensors the scene is seen through (CTL_SENSOR_*; without this call
+ * the PerspectiveSensor), called after ctl_host_scene_set_camera, whose position, target, up, fov,
+ * near / far and resolution it keeps: ctl_host_scene_compile then fills ctl_camera's sample_to_camera,
+ * dx and dy by that type's Update() (thin lens as perspective; orthographic and telecentric from
+ * float4x4::orthographic(near, far), for which the reference's constructors take near = 0.00001,
+ * Sensor.h:380, 462; spherical reads none) and hands out the ctl_sensor record.  screen_scale may be
+ * NULL for (1, 1).  Refuses, with ctl_host_last_error naming the field: a call before set_camera, a
+ * type outside 1-5, a non-finite or negative aperture_radius, a non-finite or non-positive
+ * focus_distance (types 3, 5) or screen_scale (type 5). */
+CTL_API ctl_status ctl_host_scene_set_sensor(ctl_host_scene* s, uint32_t type, float aperture_radius,
+                                             float focus_distance, const float screen_scale[2]);
+/* The ctl_camera and ctl_sensor records a compile would hand out now (the PerspectiveSensor's record
+ * without a set_sensor call): what a caller who changed the sensor after the compile writes into its
+ * description before ctl_scene_update(desc, 0), with no recompile. */
+CTL_API ctl_status ctl_host_scene_sensor_state(const ctl_host_scene* s, ctl_camera* camera, ctl_sensor* sensor);
 CTL_API ctl_status ctl_host_scene_set_flags(ctl_host_scene* s, uint32_t flags);
 /* DynamicScene::setEnvironementMap: an InfiniteLight over image texture
  * `texture` (ctl_host_scene_add_texture) with radiance scale `scale`; the
@@ -1412,6 +1472,32 @@ CTL_API ctl_status ctl_medium_eval(ctl_ctx* ctx, const ctl_medium_query* d_queri
  * of ctl_medium_eval bit for bit. */
 CTL_API ctl_status ctl_host_medium_eval(const ctl_scene_desc* desc, const ctl_medium_query* queries, int64_t n,
                                         ctl_medium_result* results);
+/* The batch sensor entry: Sensor::sampleRay (differential = 0; what the
+ * WavefrontPathTracer calls) or Sensor::sampleRayDifferential (differential != 0;
+ * the PathTracer and the PrimTracer) of the scene's sensor, through the inline
+ * functions the kernels call (csrc/ctl_sensor.h).  A result holds the ray and,
+ * for sampleRayDifferential, rayX and rayY; has_differentials = 0 where they are
+ * not defined (sampleRay, and the spherical sensor), their fields then 0. */
+typedef struct {
+    float pixel_sample[2];
+    float aperture_sample[2];
+    uint32_t differential;
+} ctl_sensor_query;        /* 20 B */
+typedef struct {
+    float o[3], d[3];      /* ray                                                     */
+    float ox[3], dx[3];    /* rayX                                                    */
+    float oy[3], dy[3];    /* rayY                                                    */
+    uint32_t has_differentials;
+    uint32_t pad;
+} ctl_sensor_result;       /* 80 B */
+/* On the device, for the uploaded scene: d_queries and d_results are device
+ * arrays of n records. */
+CTL_API ctl_status ctl_sensor_eval(ctl_ctx* ctx, const ctl_sensor_query* d_queries, int64_t n,
+                                   ctl_sensor_result* d_results, void* stream);
+/* The same for a scene description, on the CPU (no GPU needed): the arithmetic
+ * of ctl_sensor_eval bit for bit.  Refuses a bad ctl_sensor record as the upload does. */
+CTL_API ctl_status ctl_host_sensor_eval(const ctl_scene_desc* desc, const ctl_sensor_query* queries, int64_t n,
+                                        ctl_sensor_result* results);
 /* The scalar arithmetic under every kernel, for arrays of inputs: function fn
  * of a[i] (and b[i] for the two-argument functions; b is ignored otherwise) to
  * out[i], a 32-bit word holding the float's bits or the integer result.  The
